@@ -246,6 +246,32 @@ def pairwise_section(ctx, with_reference):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results):
+    """what a caller of the timed path receives from its last step — the StitchResult of every resident plan, in plan order, as float64 /
+    float32 arrays under out_dir: per subproblem score, alignment length, route and number of paths; the aligned pairs (CL_GAP -> -1).  When
+    the pairs would take the whole file set past DUMP_BYTES, a fixed sample of their rows (seed 0) is written with the row numbers beside it"""
+    from centrolign_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    score = np.concatenate([r.score for r in results]).astype(np.float64)
+    aln_len = np.concatenate([np.diff(r.aln_off.astype(np.int64)) for r in results]).astype(np.float64)
+    route = np.concatenate([r.route for r in results]).astype(np.float32)
+    num_pw = np.concatenate([r.num_pw for r in results]).astype(np.float32)
+    pairs = np.concatenate([r.pairs.reshape(-1, 2) for r in results])
+    small = {"stitch_score": score, "stitch_aln_len": aln_len, "stitch_route": route, "stitch_num_pw": num_pw}
+    room = DUMP_BYTES - sum(a.nbytes for a in small.values()) - 4096
+    rows = np.arange(len(pairs))
+    if len(pairs) * 16 > room:
+        rows = np.sort(np.random.default_rng(0).choice(len(pairs), size=room // 24, replace=False))
+        small["stitch_pairs_rows"] = rows.astype(np.float64)
+    p = pairs[rows]
+    small["stitch_pairs"] = np.where(p == capi.CL_GAP, -1.0, p.astype(np.float64))
+    for name, a in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python -m torch.distributed.run --nproc-per-node n bench.py <the same arguments>` as a child; rank 0's JSON line goes to stdout"""
     import socket
@@ -280,7 +306,11 @@ def main():
                          "and reported in config.other_plan_layout")
     ap.add_argument("--no-shard-stitch", action="store_true",
                     help="N > 1: keep every merge's stitch batch on the rank that made it instead of dealing the subproblems of ALL batches over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's stitch results) to DIR/<name>.npy: see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare (`python bench.py --gpus N`): start the N ranks ourselves, as a CHILD process, before anything here has touched the
@@ -294,14 +324,6 @@ def main():
     n_dev = torch.cuda.device_count()
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     share = world_env > 1 and n_dev < world_env          # dry run of the multi-rank path on fewer devices: ranks share them, gloo collectives
-    # before HIP initialises (device_count above does not): independent launches overlap on separate hardware queues.  Measured on the
-    # nine concurrent stitch plans (ms per step): 4 queues 8.9, 8: 8.2, 12: 5.6, 16: 4.9, 20: 3.8, 22: 4.9, 24: 11.5, 32: 28.5 — beyond
-    # ~23 PER DEVICE the queues are oversubscribed and time-sliced, so ranks that share a device share the 20; the MSA's wall-clock does
-    # not depend on it (15.2-16.3 s for 8..23)
-    # (the library asks for 20 itself when it is loaded — cl_api.cpp, cl_library_loaded — but in this process torch has loaded the HIP runtime
-    # first, and the runtime has read its settings by then: measured 9.3 ms per step without the line below, 4.1 ms with it)
-    per_device = max(1, -(-world_env // max(1, n_dev)))
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(4, 20 // per_device)))
     rank, world, dist = cd.init_distributed(None if world_env == 1 else ("gloo" if share else "nccl"))
     if args.gpus != world and rank == 0 and world > 1:
         print("warning: --gpus %d but WORLD_SIZE %d" % (args.gpus, world), file=sys.stderr)
@@ -463,6 +485,8 @@ def main():
     stats = [p.stats() for _, p in plans]
     my_cells = sum(st["dp_cells"] for st in stats)
     elapsed, dev_ms = run_steps(plans, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [p.collect() for _, p in plans])   # (run_steps has synchronised: the results of the last timed pass)
     elapsed = cd.max_over_ranks(elapsed, dist, device="cpu" if share else "cuda")
     # round-5 verdict, weak #7: the timed region is 20 x 1.5 ms with a run-to-run spread of +-5 %.  `value` stays the contract's ONE block of K steps (above); four more
     # blocks of K steps follow, and the line carries the minimum and the median of the five so that a reader sees where the headline block fell

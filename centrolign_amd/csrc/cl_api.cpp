@@ -158,11 +158,8 @@ void cl_big_free(void* p) noexcept {
 }
 
 // A context keeps up to seven streams busy (the chaining DP: walk, two far launches, the sealing stream, copies) and an MSA runs several worker
-// contexts; HIP's default of 4 hardware queues per process makes their launches queue up behind one another.  Measured on the nine concurrent
-// stitch plans of 10 x 1 Mbp (ms per pass): 4 queues 8.9, 16: 4.9, 20: 3.8, 24: 11.5 (beyond ~23 the queues are time-sliced).  The runtime reads the
-// variable when it initialises, i.e. at the first HIP call of the process: setting it when this library is loaded is early enough unless the
-// host application has already used HIP (then it keeps what it has; set GPU_MAX_HW_QUEUES yourself).  Never overrides the user.
-__attribute__((constructor)) static void cl_library_loaded() { setenv("GPU_MAX_HW_QUEUES", "20", 0); }
+// contexts; they share the process's hardware queues (GPU_MAX_HW_QUEUES, HIP's default 4).  The library leaves that setting to the host
+// application; nothing here depends on a stream having a queue of its own.
 
 void cl_set_error(cl_context* ctx, const char* fmt, ...) {
     char buf[512];

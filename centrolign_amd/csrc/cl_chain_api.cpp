@@ -1518,7 +1518,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
             for (uint32_t m = 0; m < peers.n && he == hipSuccess; ++m) {
                 if (m == peers.me) continue;
                 for (uint32_t f = 0; f < far_lag && he == hipSuccess; ++f)
-                    he = hipStreamWaitValue32(ctx->aux[f], peers.flags + kPeerDoneAt + m, peers.last_shared_epoch, hipStreamWaitValueGte, 0xFFFFFFFFu);
+                    he = cl_peer_wait_word(ctx, ctx->aux[f], m, peers.flags + kPeerDoneAt + m, peers.last_shared_epoch);
             }
             peers.last_shared_epoch = share_epoch;
         }
@@ -1594,7 +1594,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
                         for (uint32_t m = 0; m < peers.n; ++m) if (m != peers.me) Fk.peer_out[o++] = peers.peer_inbox[m] + (size_t)slot * kPeerSlotInts;
                         if (he == hipSuccess) he = cl_chain_far_launch(D, Fk, first, count, near_lo, far_stream, nullptr);
                         for (uint32_t m = 0; m < peers.n && he == hipSuccess; ++m)
-                            if (m != peers.me) he = hipStreamWriteValue32(far_stream, peers.peer_flags[m] + (size_t)peers.me * kPeerRing + slot, word, 0);
+                            if (m != peers.me) he = cl_peer_store_word_op(far_stream, peers.peer_flags[m] + (size_t)peers.me * kPeerRing + slot, word);
                         ++peers.shared_far_launches;
                     }
                 } else if (use_far) {
@@ -1644,7 +1644,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
                 // the other members' combinations of this macro-block: wait for their arrival words, fold their slot into the running maxima
                 const uint32_t slot = (k + (kPeerRing / 2) * (share_epoch & 1u)) % kPeerRing, word = (share_epoch << 20) | (k + 1);
                 for (uint32_t m = 0; m < peers.n && he == hipSuccess; ++m)
-                    if (m != peers.me) he = hipStreamWaitValue32(ctx->stream, peers.flags + (size_t)m * kPeerRing + slot, word, hipStreamWaitValueGte, 0xFFFFFFFFu);
+                    if (m != peers.me) he = cl_peer_wait_word(ctx, ctx->stream, m, peers.flags + (size_t)m * kPeerRing + slot, word);
                 if (he == hipSuccess) he = cl_chain_far_merge(D, peers.inbox + (size_t)slot * kPeerSlotInts, first, count, peers.n, peers.me, ctx->stream);
                 ++peers.merged_blocks;
             }
@@ -1663,7 +1663,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
         }
         if (shared) {   // this member has folded every slot of the DP (stream order: behind its last walk)
             for (uint32_t m = 0; m < peers.n && he == hipSuccess; ++m)
-                if (m != peers.me) he = hipStreamWriteValue32(ctx->stream, peers.peer_flags[m] + kPeerDoneAt + peers.me, share_epoch, 0);
+                if (m != peers.me) he = cl_peer_store_word_op(ctx->stream, peers.peer_flags[m] + kPeerDoneAt + peers.me, share_epoch);
         }
         if (use_far && he == hipSuccess) he = hipStreamSynchronize(seal_stream);
         // (the walk path's events are the context's ring events: nothing to destroy)

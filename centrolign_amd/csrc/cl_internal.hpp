@@ -53,6 +53,7 @@ struct cl_context {
         uint32_t* flags = nullptr;
         int* peer_inbox[8] = {};       // the other members' inboxes and arrival words as this process sees them (index = member)
         uint32_t* peer_flags[8] = {};
+        bool local[8] = {};            // member m is a context of this process (its waits are ordered behind its stores on the host: cl_peer_wait_word)
         uint32_t epoch = 0;            // one per shared DP, the same on every member; arrival words hold epoch << 20 | macro-block + 1
         uint32_t last_shared_epoch = 0; // the shared DP before this one (its "done" words are what the next one's peer stores wait for)
         uint32_t epoch_mark = 0;       // the highest epoch this context's inbox has ever been used with: the arrival words are never reset, so a group's
@@ -133,6 +134,10 @@ struct ClFallbackCounters { std::atomic<uint64_t> strip_fallbacks{0}, walk_stall
 extern ClFallbackCounters cl_fallbacks;
 
 void cl_peers_release(cl_context* ctx);         // cl_peer_api.cpp
+// the stream memory operations between the members of a merge group (cl_peer_api.cpp): an arrival word stored into another member's memory,
+// and a wait for member m's arrival word in this context's own memory
+hipError_t cl_peer_store_word_op(hipStream_t stream, uint32_t* word, uint32_t value);
+hipError_t cl_peer_wait_word(cl_context* ctx, hipStream_t stream, uint32_t member, uint32_t* word, uint32_t value);
 struct cl_polish_params;
 int cl_polish_cyclized_graph_workers(cl_context* const* ctxs, unsigned n_ctx, const cl_base_graph* graph, const char* const* path_names, const char* newick,
                                      const char* const* sequence_names, uint64_t n_sequences, const cl_merge_params* mp, const cl_polish_params* pp,

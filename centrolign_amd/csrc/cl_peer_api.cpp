@@ -16,6 +16,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <condition_variable>
 #include <cstring>
 
 #include "chain_device.h"
@@ -37,6 +38,42 @@ constexpr uint32_t kMagic = 0x434C5045u;
 constexpr size_t kInboxInts = (size_t)kPeerRing * kPeerSlotInts;
 constexpr size_t kFlagWords = kPeerFlagWords, kTestWords = kPeerTestWords, kTestInts = kPeerTestInts, kTailWords = kPeerTailWords;   // (chain_device.h)
 static_assert(((kInboxInts + kPeerStealAt) * sizeof(uint32_t)) % 8 == 0, "the steal counter is a 64-bit word");
+
+// Members of one group may be contexts of ONE process (threads).  The HIP runtime spreads a process's streams over a few hardware queues
+// (GPU_MAX_HW_QUEUES, 4 by default) and a hipStreamWaitValue32 holds up every later packet of its queue until its word arrives: had one thread
+// enqueued its wait before another member's thread enqueued the store it waits for, on a queue the two streams share, the store would sit
+// behind the wait for ever.  So every arrival store is noted here once it has been enqueued (word -> highest value), and a wait for a member of
+// this process is enqueued only when the note for its value is there: every wait follows its store in enqueue order, however the streams share
+// queues.  A member in another process has queues of its own and needs no note.
+std::mutex g_note_mutex;
+std::condition_variable g_note_cv;
+std::unordered_map<const uint32_t*, uint32_t> g_notes;
+}
+
+hipError_t cl_peer_store_word_op(hipStream_t stream, uint32_t* word, uint32_t value) {
+    const hipError_t he = hipStreamWriteValue32(stream, word, value, 0);
+    if (he != hipSuccess) return he;
+    {
+        std::lock_guard<std::mutex> lock(g_note_mutex);
+        uint32_t& v = g_notes[word];
+        if (value > v) v = value;
+    }
+    g_note_cv.notify_all();
+    return hipSuccess;
+}
+
+hipError_t cl_peer_wait_word(cl_context* ctx, hipStream_t stream, uint32_t member, uint32_t* word, uint32_t value) {
+    if (ctx->peers.local[member]) {
+        // (the same limit as the chaining DP's wait for the others: a member that has failed never enqueues its store)
+        static const double limit_s = [] { const char* e = getenv("CL_PEER_TIMEOUT_S"); const double v = e ? atof(e) : 600.0; return v > 0 ? v : 600.0; }();
+        std::unique_lock<std::mutex> lock(g_note_mutex);
+        const bool noted = g_note_cv.wait_for(lock, std::chrono::duration<double>(limit_s), [&] {
+            const auto it = g_notes.find(word);
+            return value == 0 || (it != g_notes.end() && it->second >= value);
+        });
+        if (!noted) return hipErrorLaunchTimeOut;
+    }
+    return hipStreamWaitValue32(stream, word, value, hipStreamWaitValueGte, 0xFFFFFFFFu);
 }
 
 extern "C" {
@@ -72,13 +109,13 @@ int cl_context_peer_group(cl_context* ctx, uint32_t n_members, uint32_t my_index
     if (!P.inbox) { cl_set_error(ctx, "cl_context_peer_group: cl_context_peer_export has not been called on this context"); return CL_ERR_INVALID_ARGUMENT; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (uint32_t m = 0; m < n_members; ++m) {
-        P.peer_inbox[m] = nullptr; P.peer_flags[m] = nullptr;
+        P.peer_inbox[m] = nullptr; P.peer_flags[m] = nullptr; P.local[m] = false;
         if (m == my_index) continue;
         HandleBody h;
         memcpy(&h, &members[m], sizeof(h));
         if (h.magic != kMagic) { cl_set_error(ctx, "cl_context_peer_group: member %u is not a handle of cl_context_peer_export", m); return CL_ERR_INVALID_ARGUMENT; }
         void* base = nullptr;
-        if (h.pid == (uint64_t)getpid()) base = (void*)(uintptr_t)h.ptr;   // a context of this process: its pointer is ours too
+        if (h.pid == (uint64_t)getpid()) { base = (void*)(uintptr_t)h.ptr; P.local[m] = true; }   // a context of this process: its pointer is ours too
         else {
             const std::string key(reinterpret_cast<const char*>(&h.ipc), sizeof(h.ipc));
             for (auto& o : P.opened) if (o.first == key) base = o.second;
@@ -119,10 +156,10 @@ int cl_context_peer_selftest(cl_context* ctx, uint32_t token, uint32_t timeout_m
         if (m == P.me) continue;
         uint32_t* their_ints = P.peer_flags[m] + kFlagWords + kTestWords;
         HIP_TRY(ctx, cl_peer_store_word(their_ints + 8 * P.me, token, s));                         // a kernel's store into the other device
-        HIP_TRY(ctx, hipStreamWriteValue32(s, P.peer_flags[m] + kFlagWords + P.me, token, 0));   // then the arrival word
+        HIP_TRY(ctx, cl_peer_store_word_op(s, P.peer_flags[m] + kFlagWords + P.me, token));     // then the arrival word
     }
     for (uint32_t m = 0; m < P.n; ++m)
-        if (m != P.me) HIP_TRY(ctx, hipStreamWaitValue32(s, P.flags + kFlagWords + m, token, hipStreamWaitValueGte, 0xFFFFFFFFu));
+        if (m != P.me) HIP_TRY(ctx, cl_peer_wait_word(ctx, s, m, P.flags + kFlagWords + m, token));
     uint32_t* host = static_cast<uint32_t*>(cl_pinned(ctx, kTestInts * sizeof(uint32_t)));
     if (!host) { cl_set_error(ctx, "cl_context_peer_selftest: no page-locked memory"); return CL_ERR_OUT_OF_MEMORY; }
     HIP_TRY(ctx, hipMemcpyAsync(host, P.flags + kFlagWords + kTestWords, kTestInts * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -206,6 +243,11 @@ void cl_peers_release(cl_context* ctx) {
     auto& P = ctx->peers;
     for (auto& o : P.opened) (void)hipIpcCloseMemHandle(o.second);
     P.opened.clear();
+    if (P.flags) {   // (the memory may be handed out again: an inbox made there later starts from zero)
+        std::lock_guard<std::mutex> lock(g_note_mutex);
+        for (auto it = g_notes.begin(); it != g_notes.end();)
+            it = (it->first >= P.flags && it->first < P.flags + kTailWords) ? g_notes.erase(it) : std::next(it);
+    }
     if (P.inbox) (void)hipFree(P.inbox);
     P.inbox = nullptr; P.flags = nullptr; P.n = 0;
 }

@@ -1,7 +1,5 @@
 """developer experiment: throughput of the C2 stitch batch with D independent passes in flight (D contexts, one plan each)"""
 import os, sys, time
-if len(sys.argv) > 1:
-    os.environ["GPU_MAX_HW_QUEUES"] = sys.argv[1]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from centrolign_amd import capi
