@@ -45,6 +45,9 @@ hipError_t cl_launch_popoa_linear(int W, uint32_t n_blocks, const ClDeviceBatch&
 size_t cl_linear_workspace_bytes(uint32_t nr, uint32_t nc, int npw, int R);
 hipError_t cl_launch_popoa_linear_span(uint32_t n_blocks, const ClDeviceBatch& B, const uint32_t* plist, const ClScoreParams& P, uint32_t* sync, hipStream_t stream);
 uint32_t cl_linear_span_groups(uint32_t nr);
+uint32_t cl_chain_persistent_capacity(int device);
+hipError_t cl_launch_popoa_chain_persistent(uint32_t n_blocks, uint32_t n_tasks, const ClDeviceBatch& B, const uint32_t* plist, const uint2* tasks,
+                                            uint32_t* head, const ClScoreParams& P, hipStream_t stream);
 
 namespace {
 
@@ -722,6 +725,10 @@ struct cl_stitch_plan {
     ClStripDevice sdev{};
     DevBuf<uint32_t> d_lane_sync;                  // wide near-chain pairs (popoa_lane_kernel): progress / done words per group, zeroed in front of every launch
     DevBuf<unsigned long long> d_ticks;            // [2 per launch group] the launches' own clocks (ClDeviceBatch::ticks), zeroed in front of every pass
+    // the persistent launch of the one-wave chain kinds (popoa_chain_persistent_kernel): its task list {first into plist, kind << 24 | units}, longest first,
+    // and its two queue words (next task, workgroups done), zero between passes
+    DevBuf<uint2> d_ptasks;
+    DevBuf<uint32_t> d_phead;
     std::vector<LaunchGroup> groups;
     ClDeviceBatch dev{};
     ClScoreParams sparams{};
@@ -753,7 +760,7 @@ void plan_free(cl_stitch_plan* pl) {
     pl->d_planes.release(q); pl->d_out_pairs.release(q); pl->d_out_len.release(q); pl->d_out_status.release(q);
     pl->d_plist.release(q); pl->d_out_score.release(q); pl->d_aux.release(q);
     pl->d_strips.release(q); pl->d_strip_recs.release(q); pl->d_strip_list.release(q); pl->d_progress.release(q); pl->d_handoff.release(q);
-    pl->d_ticks.release(q); pl->d_lane_sync.release(q);
+    pl->d_ticks.release(q); pl->d_lane_sync.release(q); pl->d_ptasks.release(q); pl->d_phead.release(q);
     for (auto& g : pl->groups) {
         if (g.ev0) (void)hipEventDestroy(g.ev0);
         if (g.ev1) (void)hipEventDestroy(g.ev1);
@@ -1658,6 +1665,74 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
         if (grp.count) pl->groups.push_back(grp);
       }
     }
+    // The one-wave chain launches (popoa_linear_kernel<1>, quads, duos: tens of thousands of workgroups between them) become ONE persistent launch
+    // (popoa_chain_persistent_kernel, waves = 64 marks it): a grid of as many workgroups as are resident at once pulls tasks from the plan's task list,
+    // longest first.  Launches that share a hardware queue run one after the other; one launch less per kind is one launch less in that line, and the
+    // three kinds fill one another's tails.  A task is a run of units of one kind (a pair, a quad, a duo) of at most kChunkUnits units and kChunkSteps
+    // anti-diagonal steps (a longer unit is a task of its own): a few thousand dequeues a pass instead of one per workgroup.
+    // (only where there are two or three of the kinds: a batch of one kind keeps that kind's own launch.)  CL_STITCH_PERSISTENT=0: one launch per kind as before (A/B, parity tests)
+    static const bool persistent = [] { const char* e = getenv("CL_STITCH_PERSISTENT"); return !e || e[0] != '0'; }();
+    std::vector<uint2> ptasks;
+    if (persistent) {
+        constexpr uint32_t kChunkUnits = 8, kChunkSteps = 512;
+        std::vector<size_t> members;
+        for (size_t gi = 0; gi < pl->groups.size(); ++gi) {
+            const LaunchGroup& g = pl->groups[gi];
+            if (g.kind == CL_KIND_LINEAR && (g.waves == 1 || g.waves == 2 || g.waves == 5)) members.push_back(gi);
+        }
+        std::vector<uint64_t> task_cost;
+        LaunchGroup merged;
+        merged.kind = CL_KIND_LINEAR; merged.npw = 0; merged.waves = 64;
+        merged.first = members.empty() ? 0u : pl->groups[members[0]].first;
+        uint32_t end = merged.first;
+        bool contiguous = true;
+        for (size_t gi : members) {
+            const LaunchGroup& g = pl->groups[gi];
+            contiguous = contiguous && g.first == end;
+            end = g.first + g.count;
+            merged.cells += g.cells;
+            merged.bytes += g.bytes;
+            const uint32_t kind = g.waves == 1 ? 0u : g.waves == 2 ? 1u : 2u, per_unit = g.waves == 1 ? 1u : g.waves == 2 ? 4u : 2u;
+            auto unit_cost = [&](uint32_t at) {
+                uint64_t c = 0;
+                for (uint32_t j = 0; j < per_unit; ++j) {
+                    const uint32_t x = plist[at + j];
+                    if (x != 0xFFFFFFFFu) c = std::max<uint64_t>(c, (uint64_t)pl->desc[x].n1 + pl->desc[x].n2 + (pl->desc[x].npw == 3 ? 64 : 0));
+                }
+                return c;
+            };
+            for (uint32_t at = g.first; at < g.first + g.count;) {
+                uint32_t n = 0;
+                uint64_t cost = 0;
+                while (at + n * per_unit < g.first + g.count && n < kChunkUnits) {
+                    const uint64_t c = unit_cost(at + n * per_unit);
+                    if (n && cost + c > kChunkSteps) break;
+                    cost += c;
+                    ++n;
+                }
+                ptasks.push_back(make_uint2(at, kind << 24 | n));
+                task_cost.push_back(cost);
+                at += n * per_unit;
+            }
+        }
+        if (members.size() > 1 && contiguous) {
+            merged.count = end - merged.first;
+            std::vector<uint32_t> idx(ptasks.size());
+            for (uint32_t i = 0; i < idx.size(); ++i) idx[i] = i;
+            std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return task_cost[x] > task_cost[y]; });
+            std::vector<uint2> sorted(ptasks.size());
+            for (size_t i = 0; i < idx.size(); ++i) sorted[i] = ptasks[idx[i]];
+            ptasks.swap(sorted);
+            uint32_t capacity = cl_chain_persistent_capacity(ctx->device);   // (per plan, on the plan's device: one occupancy query)
+            if (!capacity) capacity = 2048u;
+            merged.block = (int)std::min<uint32_t>(capacity, (uint32_t)ptasks.size());   // the grid
+            merged.prog_count = (uint32_t)ptasks.size();
+            for (size_t k = members.size(); k-- > 0;) pl->groups.erase(pl->groups.begin() + (std::ptrdiff_t)members[k]);
+            pl->groups.push_back(merged);
+        } else {
+            ptasks.clear();   // (one kind or none: its own launch, as with CL_STITCH_PERSISTENT=0 — nothing to share its tail with)
+        }
+    }
     // near-chain pairs in registers: one launch per workgroup shape as well (strips of 64 rows over 1 / 4 / 16 waves), longest sweep first
     // The LONG sweeps (1 024 steps and more: a handful of pairs that bound the pass) get launches of their own whose workgroups ask for more than half a compute
     // unit's LDS: one workgroup per compute unit, so that a long sweep's waves do not share their SIMDs with another pair's (190 registers per lane leave room for two
@@ -1893,6 +1968,8 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
                                 (rc = pl->d_strip_list.upload_async(ctx, pl->strip_list)) || (rc = pl->d_progress.alloc(ctx, pl->strips.size())) ||
                                 (rc = pl->d_handoff.alloc(ctx, hand_words)))) { plan_free(pl); return rc; }
     if (lane_sync_words && (rc = pl->d_lane_sync.alloc(ctx, lane_sync_words))) { plan_free(pl); return rc; }
+    const std::vector<uint32_t> phead_zero(2, 0u);
+    if (!ptasks.empty() && ((rc = pl->d_ptasks.upload_async(ctx, ptasks)) || (rc = pl->d_phead.upload_async(ctx, phead_zero)))) { plan_free(pl); return rc; }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { cl_set_error(ctx, "upload failed"); plan_free(pl); return CL_ERR_HIP; }
     { static const bool dbg = [] { const char* e = getenv("CL_STRIP_DEBUG_FAIL"); return e && *e == '1'; }(); pl->sdev.debug_fail = dbg ? 1u : 0u; }
     pl->sdev.strips = pl->d_strips.p; pl->sdev.recs = pl->d_strip_recs.p; pl->sdev.handoff = pl->d_handoff.p; pl->sdev.progress = pl->d_progress.p;
@@ -1938,6 +2015,8 @@ static hipError_t launch_group(const LaunchGroup& g, cl_stitch_plan* pl, const C
         if (e != hipSuccess) return e;
         return cl_launch_popoa_linear_span(g.count, dev, pl->d_plist.p + g.first, pl->sparams, pl->d_lane_sync.p, stream);
     }
+    if (g.kind == CL_KIND_LINEAR && g.waves == 64)
+        return cl_launch_popoa_chain_persistent((uint32_t)g.block, g.prog_count, dev, pl->d_plist.p, pl->d_ptasks.p, pl->d_phead.p, pl->sparams, stream);
     if (g.kind == CL_KIND_LINEAR) return cl_launch_popoa_linear(g.waves == 2 ? 0 : g.waves == 5 ? -2 : g.waves, g.count, dev, pl->d_plist.p + g.first, pl->sparams, stream);
     if (g.kind == CL_KIND_STRIP) {
         // the strips' progress words start every pass at zero (the strips of a launch poll one another's)
@@ -2030,6 +2109,15 @@ static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl, bool timed, bool 
         pl->tick_pass = 0;
     }
     ++pl->tick_pass;
+    // CL_STITCH_DEBUG_CLEAR=1 (tests): every pass first zeroes the plan's per-subproblem outputs, so that a pass whose launches skipped work shows up in what
+    // cl_stitch_plan_collect returns instead of leaving the previous pass's values in place
+    static const bool debug_clear = [] { const char* e = getenv("CL_STITCH_DEBUG_CLEAR"); return e && e[0] == '1'; }();
+    if (debug_clear) {
+        { int rc = cl_stitch_join(ctx); if (rc) return rc; }   // (the previous pass may still be writing them on the auxiliary streams)
+        HIP_TRY(ctx, hipMemsetAsync(pl->d_out_len.p, 0, pl->desc.size() * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(pl->d_out_status.p, 0, pl->desc.size() * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(pl->d_out_score.p, 0, pl->desc.size() * sizeof(int32_t), ctx->stream));
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     bool used[kNumAuxStreams] = {};
     // the groups come longest first (cl_stitch_plan_create: estimated duration = longest sweep x the kernel's time per step); each goes to the
@@ -2166,6 +2254,9 @@ int cl_stitch_plan_execute(cl_context* ctx, cl_stitch_plan* pl) {
     }
     HIP_TRY(ctx, hipEventRecord(pl->ev_start, ctx->stream));
     if (pl->graph_exec) {
+        // (a pass enqueued without the graph — the evented pass, a pass before the capture — may still be running on the auxiliary streams: the graph's launches use
+        // the same queue words and progress words, so it waits for them)
+        { int rc = cl_stitch_join(ctx); if (rc) return rc; }
         HIP_TRY(ctx, hipGraphLaunch(pl->graph_exec, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(pl->ev_stop, ctx->stream));
         pl->stop_pending = false;
@@ -2236,6 +2327,7 @@ int cl_stitch_plan_launch_info(cl_context* ctx, const cl_stitch_plan* pl, int in
     if (g.kind == CL_KIND_LINEAR && g.waves == 40) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_span_kernel");
     else if (g.kind == CL_KIND_LINEAR && g.waves == 2) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_quad_kernel");
     else if (g.kind == CL_KIND_LINEAR && g.waves == 5) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_duo_kernel");
+    else if (g.kind == CL_KIND_LINEAR && g.waves == 64) snprintf(out->kernel, sizeof(out->kernel), "popoa_chain_persistent_kernel");
     else if (g.kind == CL_KIND_LINEAR) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_kernel<%d>", g.waves);
     else if (g.kind == CL_KIND_LANE) snprintf(out->kernel, sizeof(out->kernel), g.block == 1 ? "popoa_lane_kernel<%d, wide>" : "popoa_lane_kernel<%d>", g.waves);
     else if (g.kind == CL_KIND_SYS) snprintf(out->kernel, sizeof(out->kernel), "popoa_sys_kernel<%d, %d>", g.npw, g.block);
@@ -2249,7 +2341,7 @@ int cl_stitch_plan_launch_info(cl_context* ctx, const cl_stitch_plan* pl, int in
     out->dp_cells = g.cells;
     out->dp_bytes = g.bytes;
     out->lds_bytes = g.kind == CL_KIND_LINEAR ? 0u : g.ring_bytes;
-    if (g.kind == CL_KIND_LINEAR && (g.waves == 2 || g.waves == 5)) {   // (the quads' and duos' lists are padded with "no pair")
+    if (g.kind == CL_KIND_LINEAR && (g.waves == 2 || g.waves == 5 || g.waves == 64)) {   // (the quads' and duos' lists are padded with "no pair")
         out->n_problems = 0;
         for (uint32_t i = g.first; i < g.first + g.count; ++i) out->n_problems += pl->plist_host[i] != 0xFFFFFFFFu;
     }

@@ -687,7 +687,73 @@ __device__ __forceinline__ void linear_pack_entry(const ClDeviceBatch& B, const 
 __global__ void __launch_bounds__(64) popoa_linear_quad_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, ClScoreParams P) { linear_pack_entry<16>(B, plist, P); }
 __global__ void __launch_bounds__(64) popoa_linear_duo_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, ClScoreParams P) { linear_pack_entry<32>(B, plist, P); }
 
+// ---- the one-wave chain kinds as ONE persistent launch ---------------------------------------------------------------------------------------------------
+// popoa_linear_kernel<1>, the quads and the duos are three launches of thousands of one-wave workgroups each: on a hardware queue that other launches share they
+// run one after the other, and each holds its queue until its last workgroup has a compute unit.  Here a grid of as many one-wave workgroups as are resident at once
+// pulls tasks from a device-side list (the plan's, longest first) until it is empty.  A task is a run of `n` consecutive units of one kind starting at plist[first]:
+// a unit is one pair (kind 0), one quad (1: four list entries) or one duo (2: two entries).  The bodies are those of the three kernels, unchanged: a workgroup is
+// one wave and runs one task at a time, so their __syncthreads and static LDS mean what they meant there.
+// head[0]: the next task; head[1]: workgroups that have found the list empty.  The last of those re-arms both words for the next pass (no memset between passes:
+// the next launch on the stream starts after this one has ended)
+__device__ __forceinline__ void chain_unit_pair(const ClDeviceBatch& B, uint32_t prob, const ClScoreParams& P) {
+    const ClProbDesc pd = B.desc[prob];
+    switch (pd.npw) {
+    case 1: linear_dispatch<1, 1>(B, pd, prob, P); break;
+    case 2: linear_dispatch<2, 1>(B, pd, prob, P); break;
+    default: linear_dispatch<3, 1>(B, pd, prob, P); break;
+    }
+}
+template <int SEG>
+__device__ __forceinline__ void chain_unit_pack(const ClDeviceBatch& B, const uint32_t* __restrict__ pack, const ClScoreParams& P) {
+    switch (B.desc[pack[0]].npw) {
+    case 1: linear_quad<1, SEG>(B, pack, P); break;
+    case 2: linear_quad<2, SEG>(B, pack, P); break;
+    default: linear_quad<3, SEG>(B, pack, P); break;
+    }
+}
+__global__ void __launch_bounds__(64) popoa_chain_persistent_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, const uint2* __restrict__ tasks,
+                                                                    uint32_t n_tasks, uint32_t* head, ClScoreParams P) {
+    cl_tick_start(B, true);
+    for (;;) {
+        uint32_t t = 0;
+        if (threadIdx.x == 0) t = atomicAdd(head, 1u);
+        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);   // (lane 0's ticket, and the compiler knows it is uniform: the dispatch below stays scalar)
+        if (t >= n_tasks) break;
+        const uint2 task = tasks[t];
+        const uint32_t kind = task.y >> 24, n = task.y & 0xFFFFFFu;
+        // (the next unit's body may reuse the static LDS word of this one's: a barrier between units)
+        if (kind == 0) for (uint32_t u = 0; u < n; ++u) { chain_unit_pair(B, plist[task.x + u], P); __syncthreads(); }
+        else if (kind == 1) for (uint32_t u = 0; u < n; ++u) { chain_unit_pack<16>(B, plist + task.x + 4u * u, P); __syncthreads(); }
+        else for (uint32_t u = 0; u < n; ++u) { chain_unit_pack<32>(B, plist + task.x + 2u * u, P); __syncthreads(); }
+    }
+    if (threadIdx.x == 0 && atomicAdd(head + 1, 1u) == gridDim.x - 1) {   // every workgroup has taken its last ticket: re-arm
+        atomicExch(head, 0u);
+        atomicExch(head + 1, 0u);
+    }
+    cl_tick_end(B, true);
+}
+
 }  // namespace
+
+// workgroups of popoa_chain_persistent_kernel resident on the device at once (0 if unknown)
+uint32_t cl_chain_persistent_capacity(int device) {
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&popoa_chain_persistent_kernel), 64, 0) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)(cus > 0 ? cus : 0);
+}
+
+// the persistent launch of the one-wave chain kinds: n_blocks workgroups pull the n_tasks tasks; head = two words, zero before the first launch
+hipError_t cl_launch_popoa_chain_persistent(uint32_t n_blocks, uint32_t n_tasks, const ClDeviceBatch& B, const uint32_t* plist, const uint2* tasks,
+                                            uint32_t* head, const ClScoreParams& P, hipStream_t stream) {
+    if (n_tasks == 0) return hipSuccess;
+    if (n_blocks == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(popoa_chain_persistent_kernel, dim3(n_blocks), dim3(64), 0, stream, B, plist, tasks, n_tasks, head, P);
+    return hipGetLastError();
+}
 
 // bytes of workspace a chain problem needs (codes + strip hand-off rows); mirrors the kernel's layout.
 // nr / nc = nodes of the graph laid across lanes / swept
