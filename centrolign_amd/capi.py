@@ -412,6 +412,43 @@ def internal_fuse(graph, pairs):
     return _take_owned_base_graph(lib, h), trans
 
 
+def induced_pairwise_cigars(graph, pairs, ctx):
+    """cl_induced_pairwise_cigars: induced_pairwise_cigar of every (path1, path2) row of `pairs` in one device pass on Context ctx; a list of
+    bytes, one CIGAR per pair.  Raises ClError with the host function's code for the first failing pair."""
+    lib = load_library()
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+    n = len(pairs)
+    g, p, off = graph.as_c(), C.c_void_p(), np.zeros(n + 1, np.uint64)
+    lib.cl_induced_pairwise_cigars.restype = C.c_int
+    lib.cl_induced_pairwise_cigars.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]
+    ctx._check(lib.cl_induced_pairwise_cigars(ctx.handle, C.byref(g), pairs.ctypes.data, n, C.byref(p), off.ctypes.data))
+    try:
+        text = C.string_at(p, int(off[-1])) if int(off[-1]) else b""
+    finally:
+        _libc_free(p)
+    return [text[int(off[k]):int(off[k + 1])] for k in range(n)]
+
+
+def induced_cyclic_maf(graph, path1, path2, name1, name2):
+    """output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), …) (src/alignment.cpp:569-904): the CLI's -A output after
+    cyclisation, for two paths of a graph that may have cycles; name1 / name2 are the paths' names.  bytes"""
+    lib = load_library()
+    g, p, n = graph.as_c(), C.c_void_p(), C.c_uint64(0)
+    lib.cl_induced_cyclic_maf.restype = C.c_int
+    lib.cl_induced_cyclic_maf.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    rc = lib.cl_induced_cyclic_maf(C.byref(g), int(path1), int(path2), _as_bytes(name1), _as_bytes(name2), C.byref(p), C.byref(n))
+    if rc != 0:
+        raise ClError(rc, "cl_induced_cyclic_maf")
+    try:
+        return C.string_at(p, int(n.value))
+    finally:
+        _libc_free(p)
+
+
+def _as_bytes(s):
+    return s if isinstance(s, bytes) else str(s).encode()
+
+
 def induced_pairwise_cigar(graph, path1, path2):
     """explicit_cigar(induced_pairwise_alignment(graph, path1, path2), …) (src/alignment.cpp:84-229): the CLI's -A output for two of the
     sequences of an acyclic MSA graph; bytes"""
@@ -1200,7 +1237,7 @@ EXPORTED_SYMBOLS = [
     "cl_extract_stitch_batch", "cl_owned_batch_view", "cl_owned_batch_free", "cl_stitch", "cl_alignment_free",
     "cl_despecify_indel_breakpoints", "cl_chain_params_default", "cl_chain_sparse_affine", "cl_chain_sparse", "cl_chain_exhaustive", "cl_chain_result_free",
     "cl_parse_fasta", "cl_fasta_free", "cl_msa_plan_create", "cl_msa_plan_free", "cl_msa_params_default", "cl_msa",
-    "cl_read_gfa", "cl_subproblem_hash_hex", "cl_internal_fuse", "cl_induced_pairwise_cigar",
+    "cl_read_gfa", "cl_subproblem_hash_hex", "cl_internal_fuse", "cl_induced_pairwise_cigar", "cl_induced_pairwise_cigars", "cl_induced_cyclic_maf",
     "cl_anchor_chain", "cl_anchor_chain_result_free", "cl_anchor_chain_masked", "cl_generate_diagonal_mask", "cl_update_mask", "cl_internal_stitch",
     "cl_partition_params_default", "cl_partition_anchors", "cl_host_route_align", "cl_stitch_rank_order",
     "cl_core_align_params_default", "cl_core_align", "cl_core_align_result_free",

@@ -361,6 +361,13 @@ struct ClPathMergeTables {
 int cl_core_align_prepared(cl_context* ctx, const cl_base_graph* g1, const cl_base_graph* g2, const cl_match_sets* matches, const cl_core_align_params* ap,
                            cl_core_align_result* out, ClPathMergeTables* ready /* may be null */);
 
+// induced_kernels.hip: the -A CIGARs of many pairs of paths (cl_induced_api.cpp).  One job per pair: path 1 and path 2 as offsets into the graph's
+// path_nodes, the word offset of path 1's position table, and (write pass) where the pair's text goes and how many bytes it has
+struct ClInducedJob { uint64_t off1, n1, off2, n2, table, text_off, text_cap; };
+hipError_t cl_launch_induced_table(const uint32_t* p1, uint64_t n1, uint32_t* pos, uint64_t n_nodes, uint32_t* repeated, hipStream_t stream);
+hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
+                                  uint64_t n_nodes, const uint32_t* tables, int64_t* text_len, char* text, hipStream_t stream);
+
 // host-side parallel loop over [0, n): f(begin, end) on up to 32 threads (the reference is single-threaded; the host glue around the device
 // passes is not part of the compared arithmetic, every iteration writes its own outputs).  The threads come from ONE pool per process
 // (cl_api.cpp), made on first use: creating and destroying threads per loop costs an mmap / munmap of every stack, and those take the

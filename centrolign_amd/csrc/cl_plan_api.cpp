@@ -728,6 +728,36 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         if (first_rc) return fail(first_rc);
     }
     const uint64_t root = n_slots - 1;
+    // Core::output_pairwise_alignments (src/core.cpp:523-591): the file of pair (p1, p2) of the root's paths, '/' in the names read as '_'
+    const bool induced = params->induced_pairwise_prefix && *params->induced_pairwise_prefix;
+    auto induced_file = [&](uint64_t p1, uint64_t p2, const char* suffix) {
+        std::string n1 = fa.names[paths[root][p1]], n2 = fa.names[paths[root][p2]];
+        std::replace(n1.begin(), n1.end(), '/', '_');
+        std::replace(n2.begin(), n2.end(), '/', '_');
+        return std::string(params->induced_pairwise_prefix) + "_" + n1 + "_" + n2 + suffix;
+    };
+    if (induced) {   // output_pairwise_alignments(false): from the acyclic root graph, before the bonds are applied (core.cpp:82-85)
+        cl_base_graph g;
+        cl_owned_base_graph_view(graph[root], &g);
+        std::vector<uint64_t> pairs;
+        for (uint64_t p1 = 0; p1 < g.n_paths; ++p1)
+            for (uint64_t p2 = p1 + 1; p2 < g.n_paths; ++p2) { pairs.push_back(p1); pairs.push_back(p2); }
+        const uint64_t n_pairs = pairs.size() / 2;
+        std::vector<uint64_t> off(n_pairs + 1);
+        char* text = nullptr;
+        if ((rc = cl_induced_pairwise_cigars(ctx, &g, pairs.data(), n_pairs, &text, off.data()))) {
+            cl_set_error(ctx, "induced pairwise alignments of the root graph failed");
+            return fail(rc);
+        }
+        for (uint64_t k = 0; k < n_pairs && rc == CL_OK; ++k) {
+            const std::string name = induced_file(pairs[2 * k], pairs[2 * k + 1], ".txt");
+            std::ofstream out(name, std::ios::binary);
+            if (out) { out.write(text + off[k], (std::streamsize)(off[k + 1] - off[k])); out << '\n'; }
+            if (!out) { cl_set_error(ctx, "could not write to induced pairwise alignment file %s", name.c_str()); rc = CL_ERR_INVALID_ARGUMENT; }
+        }
+        free(text);
+        if (rc) return fail(rc);
+    }
     if (cyclize && !bond_alns.empty()) {   // Core::apply_bonds (src/core.cpp:594-648)
         const auto tc = now();
         cl_base_graph g;
@@ -761,6 +791,36 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         st.cyclize_s = secs(tc);
     }
     free_bonds();
+    if (induced && cyclize) {   // output_pairwise_alignments(true): from the cyclised and polished graph, bonds or none (core.cpp:87-92), pairs over the host pool
+        cl_base_graph g;
+        cl_owned_base_graph_view(graph[root], &g);
+        std::vector<uint64_t> pairs;
+        for (uint64_t p1 = 0; p1 < g.n_paths; ++p1)
+            for (uint64_t p2 = p1 + 1; p2 < g.n_paths; ++p2) { pairs.push_back(p1); pairs.push_back(p2); }
+        std::atomic<int> first_rc{CL_OK};
+        std::mutex err_mutex;
+        std::string err_file;
+        cl_parallel_for(pairs.size() / 2, [&](uint64_t b, uint64_t e) {
+            for (uint64_t k = b; k < e && first_rc.load() == CL_OK; ++k) {
+                const uint64_t p1 = pairs[2 * k], p2 = pairs[2 * k + 1];
+                const std::string name = induced_file(p1, p2, ".maf");
+                char* text = nullptr;
+                uint64_t n = 0;
+                int r = cl_induced_cyclic_maf(&g, p1, p2, fa.names[paths[root][p1]], fa.names[paths[root][p2]], &text, &n);
+                if (r == CL_OK) {
+                    std::ofstream out(name, std::ios::binary);
+                    if (out) out.write(text, (std::streamsize)n);
+                    if (!out) r = CL_ERR_INVALID_ARGUMENT;
+                }
+                free(text);
+                if (r != CL_OK) {
+                    std::lock_guard<std::mutex> lock(err_mutex);
+                    if (first_rc.load() == CL_OK) { err_file = name; first_rc = r; }
+                }
+            }
+        }, 1);
+        if ((rc = first_rc.load())) { cl_set_error(ctx, "could not write the induced pairwise alignment file %s", err_file.c_str()); return fail(rc); }
+    }
     if (fa.n_sequences == 2) {
         // explicit_cigar(root.alignment, leaf of the FIRST sequence, leaf of the LAST one) (src/main.cpp:292-296)
         uint64_t first = 0, last = 0;
@@ -785,23 +845,6 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         rc = cl_write_gfa(&g, names.data(), 1, text_out, len_out);
     }
     if (rc) { cl_set_error(ctx, "writing the output failed"); return fail(rc); }
-    if (params->induced_pairwise_prefix && *params->induced_pairwise_prefix) {   // Core::output_pairwise_alignments(false)
-        cl_base_graph g;
-        cl_owned_base_graph_view(graph[root], &g);
-        for (uint64_t p1 = 0; p1 < g.n_paths; ++p1)
-            for (uint64_t p2 = p1 + 1; p2 < g.n_paths; ++p2) {
-                std::string n1 = fa.names[paths[root][p1]], n2 = fa.names[paths[root][p2]];
-                std::replace(n1.begin(), n1.end(), '/', '_');
-                std::replace(n2.begin(), n2.end(), '/', '_');
-                const std::string name = std::string(params->induced_pairwise_prefix) + "_" + n1 + "_" + n2 + ".txt";
-                char* text = nullptr;
-                if ((rc = cl_induced_pairwise_cigar(&g, p1, p2, &text, nullptr))) { cl_set_error(ctx, "induced pairwise alignment of %s and %s failed", n1.c_str(), n2.c_str()); return fail(rc); }
-                std::ofstream out(name);
-                if (!out) { free(text); cl_set_error(ctx, "could not write to induced pairwise alignment file %s", name.c_str()); return fail(CL_ERR_INVALID_ARGUMENT); }
-                out << text << '\n';
-                free(text);
-            }
-    }
     st.total_s = secs(t_all);
     if (stats) *stats = st;
     fail(CL_OK);

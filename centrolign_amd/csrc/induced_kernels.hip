@@ -1,0 +1,278 @@
+// induced_kernels.hip — the -A output of an acyclic MSA graph for many pairs of paths at once: induced_pairwise_alignment (src/alignment.cpp:130-224)
+// printed as explicit_cigar (include/centrolign/alignment.hpp:2804-2843).  The host restatement is cl_induced_pairwise_cigar (cl_io_api.cpp); the
+// entry point is cl_induced_pairwise_cigars (cl_induced_api.cpp).
+//
+// The reference's loop over path 2 has a parallel form.  Step i of path 2 meets path 1 at a_i = pos1[path2[i]] or not at all.  Matched steps, in
+// order and numbered k = 0, 1, ..., are emitted at path-1 index e_k = max(j_k, a_k) with j_{k+1} = e_k + 1 and j_0 = 0, i.e.
+//     e_k = k + max(0, max_{m <= k} (a_m - m))
+// (the reference never moves j backwards: a step that meets path 1 behind j is paired with j itself).  That is a prefix scan of (count, last matched
+// step, max(a - rank)) along path 2.  The gap run in front of match k holds the unmatched path-2 steps since the previous match and the e_k - j_k
+// skipped path-1 steps; the consolidation rule of :170-224 decides the run on its own (equal counts of at most 4: pairs at last + n + 1, compared
+// by label; otherwise all deletions, then all insertions), and the path-2 run after the last match is handled the same way against the rest of
+// path 1.  So every matched step yields at most five op tokens, each decided by the step's scan prefix and the labels it reads.
+//
+// The CIGAR is the run-length encoding of the token stream.  A second scan over (columns, first run start, last run start, text of the runs
+// completed in between, last run's op) — a monoid — gives every run's start column and every completed run's text offset.  Two passes of the
+// same kernel: the first one only counts each pair's text bytes, the second one writes each run's text when the next run begins.  No array of
+// columns or runs is ever stored: per pair the device holds the position table of its path 1 and its own text.
+//
+// One 1024-thread workgroup per pair walks path 2 in tiles of 4096 steps (4 consecutive steps per thread, two block scans per tile, carries in
+// registers).  The gather through pos1 is the only random access; path 2, and path 1 at the emitted indices, stream.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "cl_internal.hpp"
+
+namespace {
+
+constexpr uint32_t kThreads = 1024, kWaves = kThreads / 64, kItems = 4, kTile = kThreads * kItems;
+constexpr uint32_t kNoPos = 0xFFFFFFFFu;
+constexpr int64_t kNegInf = INT64_MIN / 4;
+enum : uint32_t { kOpEq = 0, kOpX = 1, kOpD = 2, kOpI = 3, kOpNone = 4 };
+
+__device__ __forceinline__ int64_t shfl_up64(int64_t v, unsigned d) { return (int64_t)__shfl_up((long long)v, d, 64); }
+
+__device__ __forceinline__ int64_t n_digits(int64_t v) {
+    int64_t d = 1;
+    while (v >= 10) { v /= 10; ++d; }
+    return d;
+}
+__device__ __forceinline__ int64_t run_width(int64_t len) { return n_digits(len) + 1; }
+
+// scan 1, over path 2: matched steps so far, the last of them, max(a - rank) over them (ranks local to the segment)
+struct MatchScan {
+    int64_t cnt, last, best;
+    static __device__ MatchScan ident() { return {0, -1, kNegInf}; }
+    __device__ MatchScan up(unsigned d) const { return {shfl_up64(cnt, d), shfl_up64(last, d), shfl_up64(best, d)}; }
+};
+__device__ __forceinline__ MatchScan combine(const MatchScan& a, const MatchScan& b) {
+    return {a.cnt + b.cnt, a.last > b.last ? a.last : b.last, a.best > b.best - a.cnt ? a.best : b.best - a.cnt};
+}
+
+// scan 2, over the op tokens: columns, the first and last run start (relative to the segment, -1: none), text bytes of the runs that begin at
+// or after the first start and end at the last one, and the op of the last run begun
+struct RunScan {
+    int64_t cols, first, last, text;
+    uint32_t last_op;
+    static __device__ RunScan ident() { return {0, -1, -1, 0, kOpNone}; }
+    __device__ RunScan up(unsigned d) const {
+        return {shfl_up64(cols, d), shfl_up64(first, d), shfl_up64(last, d), shfl_up64(text, d), (uint32_t)__shfl_up((int)last_op, d, 64)};
+    }
+};
+__device__ __forceinline__ RunScan combine(const RunScan& a, const RunScan& b) {
+    if (b.first < 0) return {a.cols + b.cols, a.first, a.last, a.text, a.last_op};
+    if (a.first < 0) return {a.cols + b.cols, a.cols + b.first, a.cols + b.last, b.text, b.last_op};
+    return {a.cols + b.cols, a.first, a.cols + b.last, a.text + b.text + run_width(a.cols + b.first - a.last), b.last_op};
+}
+
+template <class T>
+__device__ __forceinline__ T wave_inclusive(T v, unsigned lane) {
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const T o = v.up(d);
+        if (lane >= d) v = combine(o, v);
+    }
+    return v;
+}
+
+// exclusive prefix of v over the workgroup in thread order, and the workgroup's total; lds: kWaves entries
+template <class T>
+__device__ __forceinline__ T block_exclusive(T v, T* lds, T& total) {
+    const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const T inc = wave_inclusive(v, lane);
+    if (lane == 63) lds[w] = inc;
+    __syncthreads();
+    if (w == 0) {
+        T x = lane < kWaves ? lds[lane] : T::ident();
+        x = wave_inclusive(x, lane);
+        if (lane < kWaves) lds[lane] = x;
+    }
+    __syncthreads();
+    const T before = w ? lds[w - 1] : T::ident();
+    total = lds[kWaves - 1];
+    T ex = inc.up(1);
+    if (lane == 0) ex = T::ident();
+    __syncthreads();
+    return combine(before, ex);
+}
+
+struct PairView {
+    const uint32_t* p1;
+    const uint32_t* p2;
+    const uint32_t* steps_end;   // end of the graph's path_nodes
+    const uint8_t* label;
+    uint64_t n_nodes;
+    int64_t n1, n2;
+};
+
+// '=' or 'X' for path-1 index x1 against path-2 index x2 (0 <= x2 < n2).  x1 can lie past path 1 when path 2 meets path 1's nodes out of order or
+// more than once: the host function then reads on into the flat path array, and so does this, as long as that stays inside the array.
+__device__ __forceinline__ uint32_t pair_op(const PairView& v, int64_t x1, int64_t x2) {
+    const uint32_t* q = v.p1 + x1;
+    if (q >= v.steps_end) return kOpX;
+    const uint32_t u1 = *q, u2 = v.p2[x2];
+    if (u1 >= v.n_nodes) return kOpX;
+    return v.label[u1] == v.label[u2] ? kOpEq : kOpX;
+}
+
+// the consolidated gap run behind (last1, last2) with g1 unmatched path-2 steps and g2 skipped path-1 steps (alignment.cpp:170-224)
+template <class F>
+__device__ __forceinline__ void gap_run_tokens(const PairView& v, int64_t last1, int64_t last2, int64_t g1, int64_t g2, F&& tok) {
+    if (g1 == g2 && g1 <= 4) {
+        for (int64_t n = 0; n < g1; ++n) tok(pair_op(v, last1 + n + 1, last2 + n + 1), (int64_t)1);
+    } else {
+        if (g2) tok((uint32_t)kOpD, g2);
+        if (g1) tok((uint32_t)kOpI, g1);
+    }
+}
+
+// matched step s with scan-1 prefix x (exclusive) and position a on path 1: the op of the match before it (kOpNone: none), and its tokens
+__device__ __forceinline__ uint32_t previous_match_op(const PairView& v, const MatchScan& x) {
+    return x.cnt > 0 ? pair_op(v, x.cnt - 1 + (x.best > 0 ? x.best : 0), x.last) : (uint32_t)kOpNone;
+}
+template <class F>
+__device__ __forceinline__ void match_tokens(const PairView& v, const MatchScan& x, int64_t s, int64_t a, F&& tok) {
+    const int64_t k = x.cnt;
+    const int64_t best = x.best > a - k ? x.best : a - k;
+    const int64_t e = k + (best > 0 ? best : 0);
+    const int64_t e_prev = k > 0 ? k - 1 + (x.best > 0 ? x.best : 0) : -1;
+    gap_run_tokens(v, e_prev, x.last, s - x.last - 1, e - e_prev - 1, tok);
+    tok((uint32_t)pair_op(v, e, s), (int64_t)1);
+}
+
+// the run scan element of a token sequence that follows a run of op `cur`
+struct RunBuilder {
+    RunScan r;
+    uint32_t cur;
+    __device__ explicit RunBuilder(uint32_t prev_op) : r(RunScan::ident()), cur(prev_op) {}
+    __device__ void operator()(uint32_t op, int64_t cnt) {
+        if (op != cur) {
+            if (r.last >= 0) r.text += run_width(r.cols - r.last);
+            if (r.first < 0) r.first = r.cols;
+            r.last = r.cols;
+            r.last_op = op;
+            cur = op;
+        }
+        r.cols += cnt;
+    }
+};
+
+// the same tokens continuing the absolute state p (p.last, p.last_op: the run in progress; p.text: its text offset): a finished run is written out
+struct RunWriter {
+    RunScan p;
+    char* out;
+    int64_t cap;
+    __device__ void put(int64_t len, uint32_t op) {
+        const int64_t w = run_width(len);
+        if (p.text + w <= cap) {
+            for (int64_t i = w - 2; i >= 0; --i) { out[p.text + i] = (char)('0' + len % 10); len /= 10; }
+            out[p.text + w - 1] = "=XDI"[op & 3];
+        }
+        p.text += w;
+    }
+    __device__ void operator()(uint32_t op, int64_t cnt) {
+        if (op != p.last_op) {
+            if (p.last >= 0) put(p.cols - p.last, p.last_op);
+            p.last = p.cols;
+            p.last_op = op;
+        }
+        p.cols += cnt;
+    }
+};
+
+template <bool kWrite>
+__global__ void __launch_bounds__(kThreads) induced_runs_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                               const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                               int64_t* __restrict__ text_len, char* __restrict__ text) {
+    __shared__ MatchScan lds1[kWaves];
+    __shared__ RunScan lds2[kWaves];
+    const ClInducedJob job = jobs[blockIdx.x];
+    const uint32_t* pos = tables + job.table;
+    PairView v{path_nodes + job.off1, path_nodes + job.off2, path_nodes + n_steps, label, n_nodes, (int64_t)job.n1, (int64_t)job.n2};
+    char* out = kWrite ? text + job.text_off : nullptr;
+    const int64_t cap = kWrite ? (int64_t)job.text_cap : 0;
+    MatchScan c1 = MatchScan::ident();
+    RunScan c2 = RunScan::ident();
+    for (int64_t base = 0; base < v.n2; base += kTile) {
+        const int64_t s0 = base + (int64_t)threadIdx.x * kItems;
+        uint32_t a[kItems];
+        MatchScan agg = MatchScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            a[r] = kNoPos;
+            if (s0 + r < v.n2) a[r] = pos[v.p2[s0 + r]];
+            if (a[r] != kNoPos) agg = combine(agg, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        MatchScan tot1;
+        const MatchScan pre1 = combine(c1, block_exclusive(agg, lds1, tot1));
+        c1 = combine(c1, tot1);
+        RunScan ragg = RunScan::ident();
+        MatchScan x = pre1;
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            if (a[r] == kNoPos) continue;
+            RunBuilder b(previous_match_op(v, x));
+            match_tokens(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt) { b(op, cnt); });
+            ragg = combine(ragg, b.r);
+            x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        RunScan tot2;
+        const RunScan pre2 = combine(c2, block_exclusive(ragg, lds2, tot2));
+        c2 = combine(c2, tot2);
+        if (kWrite) {
+            RunWriter wr{pre2, out, cap};   // (the run in progress is the previous match's: the same runs as RunBuilder finds)
+            x = pre1;
+#pragma unroll
+            for (uint32_t r = 0; r < kItems; ++r) {
+                if (a[r] == kNoPos) continue;
+                match_tokens(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt) { wr(op, cnt); });
+                x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+            }
+        }
+    }
+    if (threadIdx.x != 0) return;
+    // the run after the last match (alignment.cpp:164-167 and the run it ends in)
+    const int64_t k = c1.cnt;
+    const int64_t e_last = k > 0 ? k - 1 + (c1.best > 0 ? c1.best : 0) : -1;
+    const int64_t g2 = v.n1 > e_last + 1 ? v.n1 - e_last - 1 : 0, g1 = v.n2 - 1 - c1.last;
+    if (!kWrite) {
+        RunBuilder b(previous_match_op(v, c1));
+        gap_run_tokens(v, e_last, c1.last, g1, g2, [&](uint32_t op, int64_t cnt) { b(op, cnt); });
+        const RunScan all = combine(c2, b.r);
+        text_len[blockIdx.x] = all.text + (all.last >= 0 ? run_width(all.cols - all.last) : 0);
+    } else {
+        RunWriter wr{c2, out, cap};
+        gap_run_tokens(v, e_last, c1.last, g1, g2, [&](uint32_t op, int64_t cnt) { wr(op, cnt); });
+        if (wr.p.last >= 0) wr.put(wr.p.cols - wr.p.last, wr.p.last_op);
+    }
+}
+
+// pos[path1[i]] = i; a node met twice leaves one of its positions behind, which the check reads back
+__global__ void induced_scatter_kernel(const uint32_t* __restrict__ p1, uint64_t n1, uint32_t* __restrict__ pos) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * blockDim.x) pos[p1[i]] = (uint32_t)i;
+}
+__global__ void induced_check_kernel(const uint32_t* __restrict__ p1, uint64_t n1, const uint32_t* __restrict__ pos, uint32_t* __restrict__ repeated) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * blockDim.x)
+        if (pos[p1[i]] != (uint32_t)i) *repeated = 1;
+}
+
+}  // namespace
+
+hipError_t cl_launch_induced_table(const uint32_t* p1, uint64_t n1, uint32_t* pos, uint64_t n_nodes, uint32_t* repeated, hipStream_t stream) {
+    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)pos, (int)kNoPos, n_nodes, stream);
+    if (e != hipSuccess || n1 == 0) return e;
+    const unsigned grid = (unsigned)std::min<uint64_t>((n1 + 255) / 256, 4096);
+    hipLaunchKernelGGL(induced_scatter_kernel, dim3(grid), dim3(256), 0, stream, p1, n1, pos);
+    hipLaunchKernelGGL(induced_check_kernel, dim3(grid), dim3(256), 0, stream, p1, n1, pos, repeated);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
+                                  uint64_t n_nodes, const uint32_t* tables, int64_t* text_len, char* text, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    if (write) hipLaunchKernelGGL(induced_runs_kernel<true>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, text_len, text);
+    else hipLaunchKernelGGL(induced_runs_kernel<false>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, text_len, text);
+    return hipGetLastError();
+}

@@ -641,6 +641,16 @@ int cl_write_gfa(const cl_base_graph* graph, const char* const* path_names, int 
  * (src/alignment.cpp:84-229) — the pairwise alignment of two of the input sequences that the MSA graph implies.  CL_ERR_CYCLIC_GRAPH when path1
  * visits a node twice (the reference throws). */
 int cl_induced_pairwise_cigar(const cl_base_graph* graph, uint64_t path1, uint64_t path2, char** text_out, uint64_t* len_out /* may be NULL */);
+/* cl_induced_pairwise_cigar of every (pairs[2k], pairs[2k+1]), k < n_pairs, in one device pass (induced_kernels.hip).  Pairs may repeat.
+ * *text_out: one malloc'ed buffer with the CIGARs back to back (NUL after the last); offsets_out[n_pairs + 1]: where each begins, and the end.
+ * Byte for byte what cl_induced_pairwise_cigar returns for each pair; the error code is the one it returns for the first failing pair.
+ * Device memory beyond the graph's paths and labels: at most 256 MB of position tables and 256 MB of CIGAR text (or one pair's CIGAR) at a time. */
+int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, char** text_out, uint64_t* offsets_out);
+/* The -A output of the CLI after cyclisation (src/core.cpp:537-545): output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), graph,
+ * path1, path2) (src/alignment.cpp:569-904) — blocks of colinear alignment between the two paths of a graph that may have cycles; name1 / name2
+ * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
+int cl_induced_cyclic_maf(const cl_base_graph* graph, uint64_t path1, uint64_t path2, const char* name1, const char* name2, char** text_out,
+                          uint64_t* len_out /* may be NULL */);
 /* -S / -R (src/core.cpp:370-422, src/execution.cpp:222-277): a finished subproblem is written as PREFIX_<hash>.gfa with cl_write_gfa, a
  * restart loads it back with read_gfa(in) + add_sentinels(graph, 5, 6) — NOT the graph that was written: node ids follow the S lines and the
  * sentinels come last, and the run continues on that graph.  cl_read_gfa builds exactly that graph (add_sentinels = 0: read_gfa alone);
