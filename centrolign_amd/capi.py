@@ -445,6 +445,45 @@ def induced_cyclic_maf(graph, path1, path2, name1, name2):
         _libc_free(p)
 
 
+def _names_array(names):
+    return (C.c_char_p * max(len(names), 1))(*[_as_bytes(n) for n in names])
+
+
+def subalignment_text(ctx, graph1, path_names1, set1, graph2, path_names2, set2, pairs, chunk_bytes=0):
+    """cl_subalignment_text: the block Core::emit_subalignment (src/core.cpp:424-472) appends to the -s file for one merge of graph1 and graph2
+    along `pairs` (node ids, gap = 2**64 - 1), on Context ctx; set1 / set2 are the names printed under the two '# sequence set' headers.  bytes"""
+    lib = load_library()
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+    g1, g2, p, n = graph1.as_c(), graph2.as_c(), C.c_void_p(), C.c_uint64(0)
+    pn1, pn2, s1, s2 = _names_array(path_names1), _names_array(path_names2), _names_array(set1), _names_array(set2)
+    lib.cl_subalignment_text.restype = C.c_int
+    lib.cl_subalignment_text.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BaseGraphC), C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    ctx._check(lib.cl_subalignment_text(ctx.handle, C.byref(g1), pn1, s1, len(set1), C.byref(g2), pn2, s2, len(set2), pairs.ctypes.data, len(pairs),
+                                        int(chunk_bytes), C.byref(p), C.byref(n)))
+    try:
+        return C.string_at(p, int(n.value))
+    finally:
+        _libc_free(p)
+
+
+def bond_alignment_cigar(leaf, pairs, path=0):
+    """cl_bond_alignment_cigar: the content of the --bond-prefix file Core::output_bond_alignment (include/centrolign/core.hpp:426-500) writes for
+    one bond alignment of a leaf graph (node ids; on a leaf graph these are the path positions of PREFIX_bonds.txt).  bytes"""
+    lib = load_library()
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+    g, p, n = leaf.as_c(), C.c_void_p(), C.c_uint64(0)
+    lib.cl_bond_alignment_cigar.restype = C.c_int
+    lib.cl_bond_alignment_cigar.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    rc = lib.cl_bond_alignment_cigar(C.byref(g), int(path), pairs.ctypes.data, len(pairs), C.byref(p), C.byref(n))
+    if rc != 0:
+        raise ClError(rc, "cl_bond_alignment_cigar")
+    try:
+        return C.string_at(p, int(n.value))
+    finally:
+        _libc_free(p)
+
+
 def _as_bytes(s):
     return s if isinstance(s, bytes) else str(s).encode()
 
@@ -720,7 +759,8 @@ class MsaParams(C.Structure):
     _fields_ = [("merge", MergeParams), ("skip_calibration", C.c_int), ("n_workers", C.c_int), ("devices", C.POINTER(C.c_int)), ("n_devices", C.c_int),
                 ("subproblems_prefix", C.c_char_p), ("restart", C.c_int),
                 ("induced_pairwise_prefix", C.c_char_p), ("cyclize", C.c_int), ("max_tandem_duplication_search_rounds", C.c_uint64),
-                ("bonds", BondParams), ("polish", PolishParams)]
+                ("bonds", BondParams), ("polish", PolishParams),
+                ("subalignments_path", C.c_char_p), ("bonds_prefix", C.c_char_p), ("force_gfa_output", C.c_int)]
 
 
 class MsaStats(C.Structure):
@@ -1053,7 +1093,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 12    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 13    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1238,6 +1278,7 @@ EXPORTED_SYMBOLS = [
     "cl_despecify_indel_breakpoints", "cl_chain_params_default", "cl_chain_sparse_affine", "cl_chain_sparse", "cl_chain_exhaustive", "cl_chain_result_free",
     "cl_parse_fasta", "cl_fasta_free", "cl_msa_plan_create", "cl_msa_plan_free", "cl_msa_params_default", "cl_msa",
     "cl_read_gfa", "cl_subproblem_hash_hex", "cl_internal_fuse", "cl_induced_pairwise_cigar", "cl_induced_pairwise_cigars", "cl_induced_cyclic_maf",
+    "cl_subalignment_text", "cl_bond_alignment_cigar",
     "cl_anchor_chain", "cl_anchor_chain_result_free", "cl_anchor_chain_masked", "cl_generate_diagonal_mask", "cl_update_mask", "cl_internal_stitch",
     "cl_partition_params_default", "cl_partition_anchors", "cl_host_route_align", "cl_stitch_rank_order",
     "cl_core_align_params_default", "cl_core_align", "cl_core_align_result_free",
@@ -1760,10 +1801,12 @@ class Context:
             self.lib.cl_merge_result_free(C.byref(out))
 
     def msa(self, fasta_text, newick=None, max_num_match_pairs=1250000, max_count=3000, skip_calibration=False, subproblems_prefix=None,
-            restart=False, induced_pairwise_prefix=None, workers=1, cyclize=False, min_cyclizing_length=None, devices=None, chaining_algorithm=None):
+            restart=False, induced_pairwise_prefix=None, workers=1, cyclize=False, min_cyclizing_length=None, devices=None, chaining_algorithm=None,
+            subalignments_path=None, bonds_prefix=None, force_gfa_output=False):
         """the whole CLI flow in the library (cl_msa): FASTA text (+ Newick text) -> explicit CIGAR (two sequences) or GFA; returns
         (text bytes, stats dict).  cyclize = the CLI's -c, min_cyclizing_length its -y; devices = device ordinals the worker contexts are
-        spread over (worker w on devices[w % len(devices)]; one process, several GPUs)"""
+        spread over (worker w on devices[w % len(devices)]; one process, several GPUs); subalignments_path = -s, bonds_prefix = --bond-prefix,
+        force_gfa_output = --force-gfa-output"""
         raw = fasta_text.encode() if isinstance(fasta_text, str) else bytes(fasta_text)
         mp = MsaParams()
         self.lib.cl_msa_params_default(C.byref(mp))
@@ -1781,6 +1824,9 @@ class Context:
         mp.restart = int(restart)                                                             # -R
         mp.induced_pairwise_prefix = induced_pairwise_prefix.encode() if induced_pairwise_prefix else None   # -A
         mp.cyclize = int(cyclize)                                                             # -c
+        mp.subalignments_path = subalignments_path.encode() if subalignments_path else None   # -s
+        mp.bonds_prefix = bonds_prefix.encode() if bonds_prefix else None                     # --bond-prefix
+        mp.force_gfa_output = int(force_gfa_output)                                           # --force-gfa-output
         if min_cyclizing_length is not None:
             mp.bonds.min_length = float(min_cyclizing_length)                                 # -y
         p, n, st = C.c_void_p(), C.c_uint64(0), MsaStats()

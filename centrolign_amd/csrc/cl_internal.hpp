@@ -368,6 +368,18 @@ hipError_t cl_launch_induced_table(const uint32_t* p1, uint64_t n1, uint32_t* po
 hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
                                   uint64_t n_nodes, const uint32_t* tables, int64_t* text_len, char* text, hipStream_t stream);
 
+// subaln_kernels.hip: the -s lines of one merge (cl_subaln_api.cpp).  One side of the merge on the device: the per-node step table
+// ((path << 32) | step of the node's first occurrence, UINT64_MAX: on no path), the labels, and the path names back to back
+struct ClSubalnSide { const unsigned long long* table; const uint8_t* label; uint64_t n_nodes; const char* names; const uint64_t* name_off; };
+hipError_t cl_launch_subaln_step_table(const uint64_t* path_off, uint64_t n_paths, const uint32_t* path_nodes, uint64_t n_steps, uint64_t n_nodes,
+                                       unsigned long long* table, hipStream_t stream);
+// block_off: [ceil(n / cl_subaln_pairs_per_block()) + 1] words, out: every workgroup's text offset and the total; first_bad: smallest invalid pair
+hipError_t cl_launch_subaln_lengths(const ClSubalnSide& s1, const ClSubalnSide& s2, const uint64_t* pairs, uint64_t n, uint64_t* block_off,
+                                    unsigned long long* first_bad, hipStream_t stream);
+hipError_t cl_launch_subaln_write(const ClSubalnSide& s1, const ClSubalnSide& s2, const uint64_t* pairs, uint64_t n, const uint64_t* block_off,
+                                  char* text, hipStream_t stream);
+uint64_t cl_subaln_pairs_per_block();
+
 // host-side parallel loop over [0, n): f(begin, end) on up to 32 threads (the reference is single-threaded; the host glue around the device
 // passes is not part of the compared arithmetic, every iteration writes its own outputs).  The threads come from ONE pool per process
 // (cl_api.cpp), made on first use: creating and destroying threads per loop costs an mmap / munmap of every stack, and those take the

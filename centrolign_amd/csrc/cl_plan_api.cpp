@@ -448,6 +448,13 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
     cl_msa_plan plan;
     rc = cl_msa_plan_create(ctx, newick, fa.names, fa.n_sequences, &plan);
     if (rc) { cl_fasta_free(&fa); return rc; }
+    const bool subalign = params->subalignments_path && *params->subalignments_path;
+    if (subalign && std::ifstream(params->subalignments_path).good()) {   // src/main.cpp:278-282: before the restart or any other work
+        cl_set_error(ctx, "Subalignment file already exists: %s", params->subalignments_path);
+        cl_msa_plan_free(&plan);
+        cl_fasta_free(&fa);
+        return CL_ERR_INVALID_ARGUMENT;
+    }
     const uint64_t n_slots = plan.n_leaves + plan.n_merges;
     std::vector<cl_owned_base_graph*> graph(n_slots, nullptr);
     std::vector<std::vector<uint64_t>> paths(n_slots);   // sequence indices of a slot's paths, in path order
@@ -576,6 +583,27 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
                 cl_alignment_list_free(&found[i]);
             }
             if ((rc = first_rc.load())) { free_bonds(); return fail(rc); }
+            if (params->bonds_prefix && *params->bonds_prefix) {   // Core::output_bond_alignment (core.hpp:426-500, called at core.cpp:271-273), leaf by leaf
+                // the k-th alignment of a leaf counts from 0 over all its rounds; its pairs are path positions, which on a leaf graph are the node ids
+                uint64_t k = 0;
+                for (size_t j = 0; j < bond_alns.size() && rc == CL_OK; ++j) {
+                    k = j > 0 && bond_alns[j - 1].first == bond_alns[j].first ? k + 1 : 0;
+                    uint64_t leaf = 0;
+                    while (plan.leaf_sequence[leaf] != bond_alns[j].first) ++leaf;
+                    const std::string name = std::string(params->bonds_prefix) + "_" + fa.names[bond_alns[j].first] + "_cigar_" + std::to_string(k) + ".txt";
+                    cl_base_graph v;
+                    cl_owned_base_graph_view(graph[leaf], &v);
+                    char* text = nullptr;
+                    uint64_t n = 0;
+                    if ((rc = cl_bond_alignment_cigar(&v, 0, bond_alns[j].second.pairs, bond_alns[j].second.n_pairs, &text, &n)) == CL_OK) {
+                        std::ofstream out(name, std::ios::binary);
+                        if (out) out.write(text, (std::streamsize)n);
+                        if (!out) { cl_set_error(ctx, "Could not write bond alignment to %s", name.c_str()); rc = CL_ERR_INVALID_ARGUMENT; }
+                    }
+                    free(text);
+                }
+                if (rc) { free_bonds(); return fail(rc); }
+            }
             st.bonds_s = secs(tb);
         }
     }
@@ -637,6 +665,39 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         }
     }
     std::mutex state_mutex;
+    // -s (Core::emit_subalignment, src/core.cpp:424-472, called at core.hpp:361-364): a merge's block is made on its worker's context right
+    // after the merge, and appended once every earlier merge the run computes has been appended, so the file is in plan order whatever the
+    // number of workers, and a failed run leaves an unbroken prefix of it
+    std::vector<std::string> sub_block(plan.n_merges);
+    std::vector<char> sub_ready(plan.n_merges, 0);
+    uint64_t sub_next = 0;   // the first merge not yet appended (or skipped: done by a restart)
+    auto subalignment_block = [&](uint64_t k, cl_context* c, const cl_base_graph& g1, const cl_base_graph& g2, const cl_alignment& aln) -> int {
+        const uint64_t a = plan.merge_children[2 * k], b = plan.merge_children[2 * k + 1];
+        std::vector<const char*> pn1, pn2, set1, set2;
+        for (uint64_t s : paths[a]) pn1.push_back(fa.names[s]);
+        for (uint64_t s : paths[b]) pn2.push_back(fa.names[s]);
+        // Execution::leaf_descendents (src/execution.cpp:163-187) pops a stack of children: the leaves right to left
+        for (auto it = leaf_set[a].rbegin(); it != leaf_set[a].rend(); ++it) set1.push_back(fa.names[*it]);
+        for (auto it = leaf_set[b].rbegin(); it != leaf_set[b].rend(); ++it) set2.push_back(fa.names[*it]);
+        char* text = nullptr;
+        uint64_t len = 0;
+        int rc = cl_subalignment_text(c, &g1, pn1.data(), set1.data(), set1.size(), &g2, pn2.data(), set2.data(), set2.size(), aln.pairs, aln.n_pairs, 0,
+                                      &text, &len);
+        if (rc) { if (c != ctx) cl_set_error(ctx, "%s", cl_last_error(c)); return rc; }
+        std::lock_guard<std::mutex> lock(state_mutex);
+        sub_block[k].assign(text, len);
+        free(text);
+        sub_ready[k] = 1;
+        std::ofstream out;
+        for (; sub_next < plan.n_merges && (done[plan.n_leaves + sub_next] || sub_ready[sub_next]); ++sub_next) {
+            if (done[plan.n_leaves + sub_next]) continue;
+            if (!out.is_open()) out.open(params->subalignments_path, std::ios::app | std::ios::binary);
+            if (out) out.write(sub_block[sub_next].data(), (std::streamsize)sub_block[sub_next].size());
+            if (!out) { cl_set_error(ctx, "Failed to write to subalignment file %s", params->subalignments_path); return (int)CL_ERR_INVALID_ARGUMENT; }
+            std::string().swap(sub_block[sub_next]);
+        }
+        return CL_OK;
+    };
     auto do_merge = [&](uint64_t k, cl_context* c) -> int {
         const uint64_t a = plan.merge_children[2 * k], b = plan.merge_children[2 * k + 1];
         cl_base_graph g1, g2;
@@ -645,6 +706,7 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         cl_merge_result r;
         int rc = cl_merge(c, &g1, &g2, &mp, &r);
         if (rc) { if (c != ctx) cl_set_error(ctx, "%s", cl_last_error(c)); return rc; }
+        if (subalign && (rc = subalignment_block(k, c, g1, g2, r.align.alignment))) { cl_merge_result_free(&r); return rc; }
         std::lock_guard<std::mutex> lock(state_mutex);
         st.match_s += r.match_ms * 1e-3;
         st.align_s += r.align_ms * 1e-3;
@@ -821,7 +883,7 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         }, 1);
         if ((rc = first_rc.load())) { cl_set_error(ctx, "could not write the induced pairwise alignment file %s", err_file.c_str()); return fail(rc); }
     }
-    if (fa.n_sequences == 2) {
+    if (fa.n_sequences == 2 && !params->force_gfa_output) {
         // explicit_cigar(root.alignment, leaf of the FIRST sequence, leaf of the LAST one) (src/main.cpp:292-296)
         uint64_t first = 0, last = 0;
         for (uint64_t i = 0; i < plan.n_leaves; ++i) { if (plan.leaf_sequence[i] == 0) first = i; if (plan.leaf_sequence[i] == 1) last = i; }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 12   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 13   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -651,6 +651,21 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* graph, cons
  * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
 int cl_induced_cyclic_maf(const cl_base_graph* graph, uint64_t path1, uint64_t path2, const char* name1, const char* name2, char** text_out,
                           uint64_t* len_out /* may be NULL */);
+/* -s of the CLI: Core::emit_subalignment (src/core.cpp:424-472), the block one merge appends to the subalignment file.  g1 / g2 are the merge's two
+ * children, path_names1 / path_names2 their BaseGraph::path_name, set1 / set2 the leaf names printed under '# sequence set 1' / '2'
+ * (Execution::leaf_descendents: right to left), pairs[2 * n_pairs] the merge's alignment in node ids of g1 / g2 (UINT64_MAX: gap).  One line per
+ * pair: each side as path name, step and decoded base of StepIndex::path_steps(node).front() (the smallest (path, step)), or "-\t-\t-".  The
+ * lines are made on the device (subaln_kernels.hip) in chunks of at most chunk_bytes of text (0: 256 MB) plus 16 bytes per pair of the chunk.
+ * CL_ERR_INVALID_ARGUMENT for a node id >= n_nodes or a node on no path (the reference reads past a vector there); the error names the first
+ * such pair.  *text_out is malloc'ed (NUL after the last byte). */
+int cl_subalignment_text(cl_context* ctx, const cl_base_graph* g1, const char* const* path_names1, const char* const* set1, uint64_t n_set1,
+                         const cl_base_graph* g2, const char* const* path_names2, const char* const* set2, uint64_t n_set2, const uint64_t* pairs,
+                         uint64_t n_pairs, uint64_t chunk_bytes, char** text_out, uint64_t* len_out /* may be NULL */);
+/* --bond-prefix of the CLI: Core::output_bond_alignment (include/centrolign/core.hpp:426-500), the whole content of the file
+ * PREFIX_<name>_cigar_<k>.txt: explicit_cigar of the bond alignment (node ids of `leaf`, both sides on path `path`) padded with the path's
+ * leading and lagging steps as indels, and a line end; a line end alone when no pair has a node on side 1.  Host only. */
+int cl_bond_alignment_cigar(const cl_base_graph* leaf, uint64_t path, const uint64_t* pairs, uint64_t n_pairs, char** text_out,
+                            uint64_t* len_out /* may be NULL */);
 /* -S / -R (src/core.cpp:370-422, src/execution.cpp:222-277): a finished subproblem is written as PREFIX_<hash>.gfa with cl_write_gfa, a
  * restart loads it back with read_gfa(in) + add_sentinels(graph, 5, 6) — NOT the graph that was written: node ids follow the S lines and the
  * sentinels come last, and the run continues on that graph.  cl_read_gfa builds exactly that graph (add_sentinels = 0: read_gfa alone);
@@ -826,6 +841,12 @@ typedef struct cl_msa_params {
     uint64_t        max_tandem_duplication_search_rounds;   /* 3 */
     cl_bond_params   bonds;
     cl_polish_params polish;
+    const char*     subalignments_path;      /* -s: every merge the run computes appends its block (cl_subalignment_text) to this file, in plan
+                                                order whatever n_workers is; the run refuses to start if the file exists (src/main.cpp:278-282).
+                                                Merges loaded or skipped by a restart, and the realignments of -c polishing, write nothing.  NULL: off */
+    const char*     bonds_prefix;            /* --bond-prefix: with -c, PREFIX_<sequence>_cigar_<k>.txt for the k-th bond alignment found in that
+                                                sequence (cl_bond_alignment_cigar); nothing when the bonds come from a restart.  NULL: off */
+    int             force_gfa_output;        /* --force-gfa-output: the GFA of the root even for two sequences (src/main.cpp:290-301) */
 } cl_msa_params;
 void cl_msa_params_default(cl_msa_params* p);
 typedef struct cl_msa_stats {

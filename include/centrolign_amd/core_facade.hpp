@@ -7,7 +7,7 @@
 //   Core:      the two constructors (files / parsed inputs — the guide tree as Newick text, which is what Tree's constructor takes,
 //              src/tree.cpp:39-160), execute(), restart(), root_subproblem(), leaf_subproblem(name), and the public tunables
 //              skip_calibration, cyclize_tandem_duplications, threads, max_tandem_duplication_search_rounds, subproblems_prefix,
-//              induced_pairwise_prefix (core.hpp:70-103).  The configurable submodules (anchorer, partitioner, stitcher, ...) are the
+//              induced_pairwise_prefix, subalignments_filepath, bonds_prefix (core.hpp:70-103).  The configurable submodules (anchorer, partitioner, stitcher, ...) are the
 //              parameter blocks of cl_merge_params under the reference's submodule names: core.anchorer.max_num_match_pairs,
 //              core.path_match_finder.max_count, core.stitcher.alignment_params, ...
 //   Execution: finished(), next(), current(), leaf_subproblem(name), final_subproblem(), leaf_subproblems(), subproblem_hash(),
@@ -16,7 +16,8 @@
 //   Subproblem: graph, tableau, alignment, name, complete (execution.hpp:18-28) — the graph as the C ABI's flat arrays
 //              (cl_owned_base_graph + view), the alignment as AlignedPair-compatible (node, node) pairs with gap = UINT64_MAX.
 // Not mirrored: the -c flow step by step (execute() hands the whole job to cl_msa when cyclize_tandem_duplications is set and keeps
-// its text), logging, bonds_prefix / subalignments_filepath.
+// its text), logging.  subalignments_filepath (-s) and bonds_prefix (--bond-prefix) are written by cl_msa as well (execute_whole); main()'s
+// --force-gfa-output is not a Core member: output() prints the CIGAR for two sequences, as main() does without it.
 #ifndef CENTROLIGN_AMD_CORE_FACADE_HPP
 #define CENTROLIGN_AMD_CORE_FACADE_HPP
 
@@ -175,12 +176,15 @@ public:
     size_t max_tandem_duplication_search_rounds = 3;
     std::string subproblems_prefix;                // -S
     std::string induced_pairwise_prefix;           // -A
+    std::string subalignments_filepath;            // -s: every merge's base-level alignment, appended in execution order
+    std::string bonds_prefix;                      // --bond-prefix: with -c, one CIGAR file per tandem duplication found
     int device = 0;                                // which GPU
 
     // trigger the MSA (src/core.cpp:45-120): calibration, then Execution's merges in order, each one cl_merge
     void execute() {
         if (!ctx) { ctx = cl_context_create(device); if (!ctx) throw std::runtime_error(std::string("Core: ") + cl_last_error(nullptr)); }
-        if (cyclize_tandem_duplications || threads > 1 || !subproblems_prefix.empty() || !induced_pairwise_prefix.empty() || restarting) { execute_whole(); return; }
+        if (cyclize_tandem_duplications || threads > 1 || !subproblems_prefix.empty() || !induced_pairwise_prefix.empty() || restarting ||
+            !subalignments_filepath.empty() || !bonds_prefix.empty()) { execute_whole(); return; }
         if (!skip_calibration) {   // Core::calibrate_anchor_scores (src/core.cpp:122-184): the mean of the leaves' intrinsic scales, in leaf order
             double sum = 0;
             const auto leaves = execution.leaf_subproblems();
@@ -244,7 +248,7 @@ private:
         newick_text = newick;
         execution = Execution(std::move(in), newick);
     }
-    // -c, -S / -R, -A, worker threads: the library's own driver (cl_msa) runs the whole job; the root subproblem is read back from its text
+    // -c, -S / -R, -A, -s, --bond-prefix, worker threads: the library's own driver (cl_msa) runs the whole job; the root subproblem is read back from its text
     void execute_whole() {
         cl_msa_params p;
         cl_msa_params_default(&p);
@@ -255,6 +259,8 @@ private:
         p.restart = restarting;
         p.induced_pairwise_prefix = induced_pairwise_prefix.empty() ? nullptr : induced_pairwise_prefix.c_str();
         p.cyclize = cyclize_tandem_duplications;
+        p.subalignments_path = subalignments_filepath.empty() ? nullptr : subalignments_filepath.c_str();
+        p.bonds_prefix = bonds_prefix.empty() ? nullptr : bonds_prefix.c_str();
         p.max_tandem_duplication_search_rounds = max_tandem_duplication_search_rounds;
         char* text = nullptr;
         uint64_t len = 0;
