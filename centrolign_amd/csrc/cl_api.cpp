@@ -46,6 +46,9 @@ size_t cl_linear_workspace_bytes(uint32_t nr, uint32_t nc, int npw, int R);
 hipError_t cl_launch_popoa_linear_span(uint32_t n_blocks, const ClDeviceBatch& B, const uint32_t* plist, const ClScoreParams& P, uint32_t* sync, hipStream_t stream);
 uint32_t cl_linear_span_groups(uint32_t nr);
 uint32_t cl_chain_persistent_capacity(int device);
+uint32_t cl_narrow_capacity(int device, int threads, uint32_t lds_bytes);
+hipError_t cl_launch_popoa_narrow(int threads, uint32_t n_blocks, uint32_t lds_bytes, const ClNarrowRoles& R, const ClDeviceBatch& B, const uint32_t* plist,
+                                  const ClScoreParams* P, hipStream_t stream);
 hipError_t cl_launch_popoa_chain_persistent(uint32_t n_blocks, uint32_t n_tasks, const ClDeviceBatch& B, const uint32_t* plist, const uint2* tasks,
                                             uint32_t* head, const ClScoreParams& P, hipStream_t stream);
 
@@ -667,6 +670,9 @@ int64_t pure_deletion_score(size_t path_len, int npw, const cl_align_params& p) 
     return s;
 }
 
+// LaunchGroup::kind of the one popoa_narrow_kernel launch of a plan (its members: cl_stitch_plan::narrow); not a kind of subproblem
+constexpr int kLaunchNarrow = 16;
+
 struct LaunchGroup {
     int kind = 0;
     int npw = 0;
@@ -729,6 +735,8 @@ struct cl_stitch_plan {
     // and its two queue words (next task, workgroups done), zero between passes
     DevBuf<uint2> d_ptasks;
     DevBuf<uint32_t> d_phead;
+    ClNarrowRoles narrow{};                        // the members of the kLaunchNarrow group, if there is one (popoa_narrow_kernel)
+    DevBuf<ClScoreParams> d_sparams;               // ... and its copy of sparams (only where that group exists)
     std::vector<LaunchGroup> groups;
     ClDeviceBatch dev{};
     ClScoreParams sparams{};
@@ -760,7 +768,7 @@ void plan_free(cl_stitch_plan* pl) {
     pl->d_planes.release(q); pl->d_out_pairs.release(q); pl->d_out_len.release(q); pl->d_out_status.release(q);
     pl->d_plist.release(q); pl->d_out_score.release(q); pl->d_aux.release(q);
     pl->d_strips.release(q); pl->d_strip_recs.release(q); pl->d_strip_list.release(q); pl->d_progress.release(q); pl->d_handoff.release(q);
-    pl->d_ticks.release(q); pl->d_lane_sync.release(q); pl->d_ptasks.release(q); pl->d_phead.release(q);
+    pl->d_ticks.release(q); pl->d_lane_sync.release(q); pl->d_ptasks.release(q); pl->d_phead.release(q); pl->d_sparams.release(q);
     for (auto& g : pl->groups) {
         if (g.ev0) (void)hipEventDestroy(g.ev0);
         if (g.ev1) (void)hipEventDestroy(g.ev1);
@@ -1952,6 +1960,69 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
             return c * (g.kind == CL_KIND_GENERAL ? (g.ring_bytes ? 5 : 16) : 1);
         };
         for (LaunchGroup& g : pl->groups) g.est_cost = crit(g);
+        // Launches of few workgroups that last as long as their longest sweep (popoa_lane_kernel<1 / 3 / 4>, popoa_sys_kernel<NPW, 64 / 256> of few pairs) become
+        // ONE launch (popoa_narrow_kernel): launches that share a hardware queue run one after the other, and in the step of 10 x 1 Mbp lane<3> (66 workgroups,
+        // 1.3 ms), lane<1> (8, 1.0 ms) and a sys<2, 256> launch (21, 0.6 ms) held their queues for 2.9 ms together.  Every workgroup runs the body of its own
+        // launch on the same pair; a member is taken, longest sweep first, only while every workgroup of the merged launch is resident at once (compute units x
+        // the workgroups per compute unit of the merged block size and LDS), so the merged launch lasts about as long as its longest member.  The rest keep
+        // their launches.  Only in plans of 2 048 subproblems and more (the plans whose launches share the device, as lane_round_waves); CL_STITCH_NARROW=0:
+        // separate launches (A/B, parity tests)
+        static const bool narrow_on = [] { const char* e = getenv("CL_STITCH_NARROW"); return !e || e[0] != '0'; }();
+        if (narrow_on && n >= 2048) {
+            auto code_of = [](const LaunchGroup& g) -> int {
+                if (g.kind == CL_KIND_LANE && g.block == 0) return g.waves == 1 ? 0 : g.waves == 3 ? 1 : g.waves == 4 ? 2 : -1;
+                if (g.kind == CL_KIND_SYS && (g.block == 64 || g.block == 256)) return 3 + 2 * (g.npw - 1) + (g.block == 256);
+                return -1;
+            };
+            auto longest = [&](const LaunchGroup& g) {
+                uint64_t c = 0;
+                for (uint32_t i = g.first; i < g.first + g.count; ++i) c = std::max<uint64_t>(c, (uint64_t)pl->desc[plist[i]].n1 + pl->desc[plist[i]].n2);
+                return c;
+            };
+            std::vector<size_t> cand;
+            for (size_t gi = 0; gi < pl->groups.size(); ++gi) if (code_of(pl->groups[gi]) >= 0) cand.push_back(gi);
+            std::vector<uint64_t> sweep(pl->groups.size(), 0);
+            for (size_t gi : cand) sweep[gi] = longest(pl->groups[gi]);
+            std::stable_sort(cand.begin(), cand.end(), [&](size_t x, size_t y) { return sweep[x] > sweep[y]; });
+            std::vector<size_t> members;
+            uint64_t blocks = 0;
+            uint32_t lds = 0;
+            int threads = 192;
+            for (size_t gi : cand) {
+                const LaunchGroup& g = pl->groups[gi];
+                if (members.size() == (size_t)kNarrowMaxRoles) break;
+                const int t = std::max(threads, g.kind == CL_KIND_LANE ? 64 * g.waves : g.block);
+                const uint32_t l = std::max(lds, g.ring_bytes);
+                if (l > 159u * 1024u) continue;
+                const uint64_t resident = cl_narrow_capacity(ctx->device, t, l);   // (0 if the query failed: nothing merges)
+                if (blocks + g.count > resident) continue;
+                members.push_back(gi);
+                blocks += g.count;
+                lds = l;
+                threads = t;
+            }
+            if (members.size() >= 2) {
+                LaunchGroup merged;
+                merged.kind = kLaunchNarrow;
+                merged.block = threads;
+                merged.ring_bytes = lds;
+                merged.count = (uint32_t)blocks;
+                pl->narrow = ClNarrowRoles{};
+                for (size_t gi : members) {
+                    const LaunchGroup& g = pl->groups[gi];
+                    const uint32_t r = pl->narrow.n++;
+                    pl->narrow.end[r] = (r ? pl->narrow.end[r - 1] : 0u) + g.count;
+                    pl->narrow.first[r] = g.first;
+                    pl->narrow.code[r] = (uint32_t)code_of(g);
+                    merged.cells += g.cells;
+                    merged.bytes += g.bytes;
+                    merged.est_cost = std::max(merged.est_cost, g.est_cost);
+                }
+                std::sort(members.begin(), members.end());
+                for (size_t k = members.size(); k-- > 0;) pl->groups.erase(pl->groups.begin() + (std::ptrdiff_t)members[k]);
+                pl->groups.push_back(merged);
+            }
+        }
         std::stable_sort(pl->groups.begin(), pl->groups.end(), [&](const LaunchGroup& x, const LaunchGroup& y) { return x.est_cost > y.est_cost; });
     }
     pl->stats.n_launches = pl->groups.size();
@@ -1970,6 +2041,11 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
     if (lane_sync_words && (rc = pl->d_lane_sync.alloc(ctx, lane_sync_words))) { plan_free(pl); return rc; }
     const std::vector<uint32_t> phead_zero(2, 0u);
     if (!ptasks.empty() && ((rc = pl->d_ptasks.upload_async(ctx, ptasks)) || (rc = pl->d_phead.upload_async(ctx, phead_zero)))) { plan_free(pl); return rc; }
+    pl->sparams.match = (int32_t)ap.match;
+    pl->sparams.mismatch = (int32_t)ap.mismatch;
+    for (int k = 0; k < 3; ++k) { pl->sparams.oe[k] = (int32_t)(ap.gap_open[k] + ap.gap_extend[k]); pl->sparams.ext[k] = (int32_t)ap.gap_extend[k]; }
+    const std::vector<ClScoreParams> sparams_copy(1, pl->sparams);
+    if (pl->narrow.n && (rc = pl->d_sparams.upload_async(ctx, sparams_copy))) { plan_free(pl); return rc; }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { cl_set_error(ctx, "upload failed"); plan_free(pl); return CL_ERR_HIP; }
     { static const bool dbg = [] { const char* e = getenv("CL_STRIP_DEBUG_FAIL"); return e && *e == '1'; }(); pl->sdev.debug_fail = dbg ? 1u : 0u; }
     pl->sdev.strips = pl->d_strips.p; pl->sdev.recs = pl->d_strip_recs.p; pl->sdev.handoff = pl->d_handoff.p; pl->sdev.progress = pl->d_progress.p;
@@ -1990,9 +2066,6 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
     pl->dev.out_status = pl->d_out_status.p;
     { const char* e = getenv("CL_SPAN_DEBUG_FAIL"); pl->dev.debug_span_fail = e && e[0] == '1' ? 1 : 0; }   // test hook: every spanning chain pair reports status 9
     { const char* e = getenv("CL_DEBUG_SKIP_TRACEBACK"); pl->dev.skip_traceback = e ? atoi(e) : 0; }   // measurement hook: 1 no traceback, 3 also no plane stores in the systolic kernel
-    pl->sparams.match = (int32_t)ap.match;
-    pl->sparams.mismatch = (int32_t)ap.mismatch;
-    for (int k = 0; k < 3; ++k) { pl->sparams.oe[k] = (int32_t)(ap.gap_open[k] + ap.gap_extend[k]); pl->sparams.ext[k] = (int32_t)ap.gap_extend[k]; }
     if (hipEventCreate(&pl->ev_start) != hipSuccess || hipEventCreate(&pl->ev_stop) != hipSuccess) {
         set_error(ctx, "hipEventCreate failed");
         plan_free(pl);
@@ -2015,6 +2088,7 @@ static hipError_t launch_group(const LaunchGroup& g, cl_stitch_plan* pl, const C
         if (e != hipSuccess) return e;
         return cl_launch_popoa_linear_span(g.count, dev, pl->d_plist.p + g.first, pl->sparams, pl->d_lane_sync.p, stream);
     }
+    if (g.kind == kLaunchNarrow) return cl_launch_popoa_narrow(g.block, g.count, g.ring_bytes, pl->narrow, dev, pl->d_plist.p, pl->d_sparams.p, stream);
     if (g.kind == CL_KIND_LINEAR && g.waves == 64)
         return cl_launch_popoa_chain_persistent((uint32_t)g.block, g.prog_count, dev, pl->d_plist.p, pl->d_ptasks.p, pl->d_phead.p, pl->sparams, stream);
     if (g.kind == CL_KIND_LINEAR) return cl_launch_popoa_linear(g.waves == 2 ? 0 : g.waves == 5 ? -2 : g.waves, g.count, dev, pl->d_plist.p + g.first, pl->sparams, stream);
@@ -2324,7 +2398,8 @@ int cl_stitch_plan_launch_info(cl_context* ctx, const cl_stitch_plan* pl, int in
     if (!ctx || !pl || !out || index < 0 || index >= (int)pl->groups.size()) return CL_ERR_INVALID_ARGUMENT;
     const LaunchGroup& g = pl->groups[index];
     memset(out, 0, sizeof(*out));
-    if (g.kind == CL_KIND_LINEAR && g.waves == 40) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_span_kernel");
+    if (g.kind == kLaunchNarrow) snprintf(out->kernel, sizeof(out->kernel), "popoa_narrow_kernel");
+    else if (g.kind == CL_KIND_LINEAR && g.waves == 40) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_span_kernel");
     else if (g.kind == CL_KIND_LINEAR && g.waves == 2) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_quad_kernel");
     else if (g.kind == CL_KIND_LINEAR && g.waves == 5) snprintf(out->kernel, sizeof(out->kernel), "popoa_linear_duo_kernel");
     else if (g.kind == CL_KIND_LINEAR && g.waves == 64) snprintf(out->kernel, sizeof(out->kernel), "popoa_chain_persistent_kernel");
@@ -2345,11 +2420,16 @@ int cl_stitch_plan_launch_info(cl_context* ctx, const cl_stitch_plan* pl, int in
         out->n_problems = 0;
         for (uint32_t i = g.first; i < g.first + g.count; ++i) out->n_problems += pl->plist_host[i] != 0xFFFFFFFFu;
     }
-    for (uint32_t i = g.first; i < g.first + g.count; ++i) {
-        if (g.kind != CL_KIND_STRIP && pl->plist_host[i] == 0xFFFFFFFFu) continue;
+    auto sweep_of = [&](uint32_t i) {
+        if (g.kind != CL_KIND_STRIP && pl->plist_host[i] == 0xFFFFFFFFu) return;
         const ClProbDesc& d = pl->desc[g.kind == CL_KIND_STRIP ? pl->strips[pl->strip_list[i]].prob : pl->plist_host[i]];
         if (d.n1 + d.n2 > out->max_sweep) { out->max_sweep = d.n1 + d.n2; out->max_n1 = d.n1; out->max_n2 = d.n2; }
+    };
+    if (g.kind == kLaunchNarrow) {   // (the members' lists: a workgroup per pair)
+        for (uint32_t r = 0; r < pl->narrow.n; ++r)
+            for (uint32_t i = 0; i < pl->narrow.end[r] - (r ? pl->narrow.end[r - 1] : 0u); ++i) sweep_of(pl->narrow.first[r] + i);
     }
+    for (uint32_t i = g.first; g.kind != kLaunchNarrow && i < g.first + g.count; ++i) sweep_of(i);
     if (pl->profiled) out->last_ms = g.host_ms;
     if (g.evented && hipEventQuery(g.ev1) == hipSuccess) {
         float ems = 0.f;

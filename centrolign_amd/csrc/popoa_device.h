@@ -30,6 +30,17 @@ struct ClProbDesc {
     uint32_t aux_cnt;         // ... and its length
 };
 
+// popoa_narrow_kernel: several launches of few workgroups as ONE grid whose workgroups are all resident at once (cl_stitch_plan_create).  Role r owns the
+// workgroups [end[r - 1], end[r]) (end[-1] = 0) and takes the pairs plist[first[r] + ...] with the body named by code[r]: 0 / 1 / 2 = popoa_lane_kernel<1 / 3 / 4>,
+// 3 + 2 (NPW - 1) + (BLOCK == 256) = popoa_sys_kernel<NPW, BLOCK> for BLOCK 64 / 256
+constexpr int kNarrowMaxRoles = 8;
+struct ClNarrowRoles {
+    uint32_t end[kNarrowMaxRoles];
+    uint32_t first[kNarrowMaxRoles];
+    uint32_t code[kNarrowMaxRoles];
+    uint32_t n;
+};
+
 struct ClScoreParams {
     int32_t match;            // +match
     int32_t mismatch;         // -mismatch is applied by the kernels

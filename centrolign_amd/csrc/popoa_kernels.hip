@@ -698,14 +698,13 @@ __global__ void __launch_bounds__(BLOCK) popoa_ring_kernel(ClDeviceBatch B, cons
 // The int32 planes go to HBM anti-diagonal-major as before: the traceback reads them.
 // ClProbDesc::pad: bits 0-4 log2 H, bit 15: graph 2 is the shorter one (rows = graph 2: the roles of I and D swap);
 // ClProbDesc::aux_base / aux_cnt: the saved columns.
+// sys_sweep: the sweep and traceback of one pair by one workgroup of BLOCK threads (popoa_sys_kernel; popoa_narrow_kernel's sys roles)
 template <int NPW, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) popoa_sys_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, ClScoreParams P) {
+__device__ __forceinline__ void sys_sweep(const ClDeviceBatch& B, const uint32_t prob, const ClScoreParams& P) {
     extern __shared__ __attribute__((aligned(16))) int32_t lds[];
     // one cell: NumPW 1: {M, V0, H0, -}; NumPW 2, 3: {M, V0, V1, V2 | M, H0, H1, H2} — what a vertical or a horizontal read needs is one
     // aligned 16-byte LDS read
     constexpr int CW = NPW == 1 ? 4 : 8;
-    cl_tick_start(B, gridDim.x <= 4096u || (blockIdx.x & 63u) == 0);
-    const uint32_t prob = plist[blockIdx.x];
     const ClProbDesc pd = B.desc[prob];
     const DiagGeom G(pd.n1, pd.n2);
     Planes<NPW> pl;
@@ -962,6 +961,12 @@ __global__ void __launch_bounds__(BLOCK) popoa_sys_kernel(ClDeviceBatch B, const
     }
     __syncthreads();   // vmcnt(0): every plane value is in memory
     if (tid < 64 && !B.skip_traceback) traceback_wave<NPW>(B, pd, G, pl, P, prob);
+}
+
+template <int NPW, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) popoa_sys_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, ClScoreParams P) {
+    cl_tick_start(B, gridDim.x <= 4096u || (blockIdx.x & 63u) == 0);
+    sys_sweep<NPW, BLOCK>(B, plist[blockIdx.x], P);
     cl_tick_end(B, gridDim.x <= 4096u || (blockIdx.x & 63u) == 0);
 }
 
@@ -1400,7 +1405,77 @@ void launch_general_npw(int block, uint32_t n_blocks, uint32_t ring_bytes, const
 
 #include "popoa_lane.h"
 
+template <int W>
+__device__ __forceinline__ void lane_role(const ClDeviceBatch& B, uint32_t prob, const ClScoreParams& P, int32_t* lds) {
+    const ClProbDesc pd = B.desc[prob];
+    switch (pd.npw) {
+    case 1: lane_dispatch<1, W, false>(B, pd, prob, P, lds, 0u, nullptr); break;
+    case 2: lane_dispatch<2, W, false>(B, pd, prob, P, lds, 0u, nullptr); break;
+    default: lane_dispatch<3, W, false>(B, pd, prob, P, lds, 0u, nullptr); break;
+    }
+}
+
+// popoa_narrow_kernel: the launches of a stitch pass that hold few workgroups and last as long as their longest sweep (popoa_lane_kernel<1 / 3 / 4>, small
+// popoa_sys_kernel<NPW, 64 / 256> launches) as ONE grid, so that they no longer queue one behind the other on a hardware queue.  The plan only merges launches
+// whose workgroups are all resident at once (ClNarrowRoles).  A workgroup finds its role from R (kernel arguments: uniform, no load of its own) and runs that
+// kernel's body on the same plist entry as that kernel's workgroup would: same pair, same code path, same outputs.  Nothing is shared between workgroups.
+// Block = 256 threads (192 when no role needs more); a role of fewer threads ends its other waves first.  The bodies' barriers (__syncthreads,
+// s_barrier) then count only the role's own waves: s_barrier waits for the waves of the workgroup that have not ended, and an ended wave is no longer one
+// of them (CDNA3 ISA, S_BARRIER).  The exit is a scalar branch on readfirstlane values, so an ended wave reaches s_endpgm and never executes a barrier.
+// The score parameters come from a copy in HBM (the plan's): passed by value as in the other kernels, the argument was copied to scratch in this kernel
+// (32 bytes per lane, read back by every body) instead of being read where it lies.
+__global__ void __launch_bounds__(256) popoa_narrow_kernel(ClDeviceBatch B, const uint32_t* __restrict__ plist, const ClScoreParams* __restrict__ Pg, ClNarrowRoles R) {
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const ClScoreParams& P = *Pg;
+    uint32_t code = R.code[0], first = R.first[0], base = 0;
+#pragma unroll
+    for (int k = 1; k < kNarrowMaxRoles; ++k)
+        if ((uint32_t)k < R.n && blockIdx.x >= R.end[k - 1]) { code = R.code[k]; first = R.first[k]; base = R.end[k - 1]; }
+    code = __builtin_amdgcn_readfirstlane(code);
+    const uint32_t waves = code == 0 ? 1u : code == 1 ? 3u : code == 2 ? 4u : (code - 3u) & 1u ? 4u : 1u;
+    if ((uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= waves) return;
+    cl_tick_start(B, gridDim.x <= 4096u || (blockIdx.x & 63u) == 0);
+    const uint32_t prob = plist[first + blockIdx.x - base];
+    switch (code) {
+    case 0: lane_role<1>(B, prob, P, lds); break;
+    case 1: lane_role<3>(B, prob, P, lds); break;
+    case 2: lane_role<4>(B, prob, P, lds); break;
+    case 3: sys_sweep<1, 64>(B, prob, P); break;
+    case 4: sys_sweep<1, 256>(B, prob, P); break;
+    case 5: sys_sweep<2, 64>(B, prob, P); break;
+    case 6: sys_sweep<2, 256>(B, prob, P); break;
+    case 7: sys_sweep<3, 64>(B, prob, P); break;
+    default: sys_sweep<3, 256>(B, prob, P); break;
+    }
+    cl_tick_end(B, gridDim.x <= 4096u || (blockIdx.x & 63u) == 0);
+}
+
 }  // namespace
+
+// the workgroups of popoa_narrow_kernel that are resident at once on the device with `threads` threads and `lds_bytes` of dynamic LDS each (0: the query failed)
+uint32_t cl_narrow_capacity(int device, int threads, uint32_t lds_bytes) {
+    int per_cu = 0, cus = 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&popoa_narrow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&popoa_narrow_kernel), threads, lds_bytes) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)(cus > 0 ? cus : 0);
+}
+
+hipError_t cl_launch_popoa_narrow(int threads, uint32_t n_blocks, uint32_t lds_bytes, const ClNarrowRoles& R, const ClDeviceBatch& B, const uint32_t* plist,
+                                  const ClScoreParams* P, hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    if ((threads != 192 && threads != 256) || lds_bytes > 159 * 1024 || R.n < 1 || R.n > (uint32_t)kNarrowMaxRoles || R.end[R.n - 1] != n_blocks) return hipErrorInvalidValue;
+    static ClDeviceOnce attr_once;   // (the lane bodies' few bytes of static LDS beside the dynamic: 159 KB, as popoa_lane_kernel)
+    attr_once([] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&popoa_narrow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+        (void)hipGetLastError();
+    });
+    hipLaunchKernelGGL(popoa_narrow_kernel, dim3(n_blocks), dim3(threads), lds_bytes, stream, B, plist, P, R);
+    return hipGetLastError();
+}
 
 // host-callable launcher (C++ linkage, used by cl_api.cpp only)
 // ring_bytes > 0: the LDS-ring variant (every problem of the launch has its ring depth in ClProbDesc::pad and fits ring_bytes)
