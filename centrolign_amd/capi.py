@@ -1093,7 +1093,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 13    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 14    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1252,6 +1252,22 @@ def load_library(path=None):
     lib.cl_internal_stitch.restype = C.c_int
     lib.cl_internal_stitch.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StitchParams),
                                        C.POINTER(AlignmentC)]
+    lib.cl_config_default.restype = C.c_void_p
+    lib.cl_config_default.argtypes = []
+    lib.cl_config_free.restype = None
+    lib.cl_config_free.argtypes = [C.c_void_p]
+    lib.cl_config_set.restype = C.c_int
+    lib.cl_config_set.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    lib.cl_config_get.restype = C.c_int
+    lib.cl_config_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    lib.cl_config_parse.restype = C.c_int
+    lib.cl_config_parse.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.cl_config_generate.restype = C.c_int
+    lib.cl_config_generate.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.cl_config_validate.restype = C.c_int
+    lib.cl_config_validate.argtypes = [C.c_void_p]
+    lib.cl_config_msa_params.restype = C.c_int
+    lib.cl_config_msa_params.argtypes = [C.c_void_p, C.POINTER(MsaParams)]
     if path is None:
         _lib = lib
     return lib
@@ -1289,7 +1305,74 @@ EXPORTED_SYMBOLS = [
     "cl_bond_params_default", "cl_identify_bonds", "cl_bonds_free", "cl_leaf_calibrate", "cl_leaf_calibration_free", "cl_alignment_list_free",
     "cl_leaf_bond_alignments", "cl_simplify_bubbles", "cl_apply_bonds", "cl_polish_params_default", "cl_identify_inconsistencies",
     "cl_polish_cyclized_graph",
+    "cl_config_default", "cl_config_free", "cl_config_set", "cl_config_get", "cl_config_parse", "cl_config_generate", "cl_config_validate",
+    "cl_config_msa_params",
 ]
+
+
+class Config:
+    """cl_config: the CLI's parameters by name (src/parameters.cpp), read from / written to config text; host only.
+    Config() holds the CLI's starting values, Config(text) those of a config file"""
+
+    def __init__(self, text=None):
+        self.lib = load_library()
+        h = C.c_void_p()
+        if text is None:
+            h.value = self.lib.cl_config_default()
+            if not h.value:
+                raise MemoryError("cl_config_default")
+        else:
+            raw = text.encode() if isinstance(text, str) else bytes(text)
+            self._check(self.lib.cl_config_parse(raw, len(raw), C.byref(h)))
+        self.handle = h
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = self.lib.cl_last_error(None)
+            raise ClError(rc, msg.decode() if msg else "")
+
+    def _text(self, p):
+        try:
+            return C.string_at(p).decode()
+        finally:
+            _libc_free(p)
+
+    def __setitem__(self, name, value):
+        if isinstance(value, bool):
+            value = "true" if value else "false"
+        elif isinstance(value, (list, tuple)):
+            value = ",".join(str(v) for v in value)
+        self._check(self.lib.cl_config_set(self.handle, name.encode(), str(value).encode()))
+
+    def __getitem__(self, name):
+        p = C.c_void_p()
+        self._check(self.lib.cl_config_get(self.handle, name.encode(), C.byref(p)))
+        return self._text(p)
+
+    def generate(self):
+        p = C.c_void_p()
+        self._check(self.lib.cl_config_generate(self.handle, C.byref(p), None))
+        return self._text(p)
+
+    def validate(self):
+        self._check(self.lib.cl_config_validate(self.handle))
+
+    def msa_params(self):
+        """the cl_msa_params this config runs with (string fields point into this object: keep it alive while they are used)"""
+        mp = MsaParams()
+        self._check(self.lib.cl_config_msa_params(self.handle, C.byref(mp)))
+        return mp
+
+    def close(self):
+        if self.handle:
+            self.lib.cl_config_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ChainAnchorsC(C.Structure):

@@ -1,0 +1,315 @@
+// cl_cli.cpp — the `centrolign` executable: the reference's command line (src/main.cpp) over the library's C ABI.  Options and their
+// order of effect are the reference's; the parameters live in a cl_config (cl_config_api.cpp) and the run is one cl_msa call.
+// Deliberate differences from the reference (also in print_help and README.md):
+//   - every failure is "error: <message>" on stderr and exit status 1 (the reference lets some exceptions escape and aborts);
+//   - -p takes a decimal number (the reference stores an integer into a Double parameter, which its type check refuses: it aborts);
+//   - -t N runs N worker contexts; --devices LIST places them (cl_msa_params.devices);
+//   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
+#include <getopt.h>
+
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "centrolign_amd.h"
+
+namespace {
+
+enum { LOG_SILENT = 0, LOG_MINIMAL = 1, LOG_BASIC = 2, LOG_VERBOSE = 3, LOG_DEBUG = 4 };
+int g_level = LOG_BASIC;
+
+void log_line(int level, const std::string& msg) {
+    if (level <= g_level) fprintf(stderr, "[centrolign] %s\n", msg.c_str());
+}
+
+std::string lib_error() {
+    const char* e = cl_last_error(nullptr);
+    return e && *e ? e : "unknown error";
+}
+
+int fail(const std::string& msg) {
+    fprintf(stderr, "error: %s\n", msg.c_str());
+    return 1;
+}
+
+std::string config_value(const cl_config* cfg, const char* name) {
+    char* t = nullptr;
+    if (cl_config_get(cfg, name, &t)) return std::string();
+    std::string s(t);
+    free(t);
+    return s;
+}
+
+std::string generate(const cl_config* cfg) {
+    char* t = nullptr;
+    uint64_t n = 0;
+    if (cl_config_generate(cfg, &t, &n)) return std::string();
+    std::string s(t, n);
+    free(t);
+    return s;
+}
+
+// the whole of a file, or of standard input for "-"
+bool read_input(const std::string& name, std::string& out, std::string& err) {
+    FILE* f = name == "-" ? stdin : fopen(name.c_str(), "rb");
+    if (!f) {
+        err = "Could not open file " + name;
+        return false;
+    }
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.append(buf, n);
+    const bool ok = !ferror(f);
+    if (f != stdin) fclose(f);
+    if (!ok) err = "Could not read file " + name;
+    return ok;
+}
+
+bool parse_devices(const char* text, std::vector<int>& out) {
+    std::string s(text);
+    size_t pos = 0;
+    while (pos <= s.size()) {
+        size_t comma = s.find(',', pos);
+        if (comma == std::string::npos) comma = s.size();
+        const std::string tok = s.substr(pos, comma - pos);
+        char* end = nullptr;
+        errno = 0;
+        long v = strtol(tok.c_str(), &end, 10);
+        if (tok.empty() || *end || errno || v < 0 || v > 1 << 20) return false;
+        out.push_back((int)v);
+        pos = comma + 1;
+    }
+    return !out.empty();
+}
+
+void print_help(const cl_config* defaults) {
+    FILE* o = stderr;
+    fprintf(o, "\n");
+    fprintf(o, "Usage: centrolign [options] sequences.fasta\n");
+    fprintf(o, "\n");
+    fprintf(o, "Aligns the sequences of a FASTA file (- reads standard input) on an AMD Instinct GPU and writes the alignment to standard\n");
+    fprintf(o, "output: a CIGAR for two sequences, a GFA graph otherwise.\n");
+    fprintf(o, "\n");
+    fprintf(o, "Options:\n");
+    fprintf(o, " --tree / -T FILE            Newick guide tree over the FASTA's sequence names [the sequences in FASTA order]\n");
+    fprintf(o, " --all-pairs / -A PREFIX     Write the induced alignment of every pair of sequences to files starting with PREFIX\n");
+    fprintf(o, " --all-subprobs / -S PREFIX  Write the alignment of every subtree to files starting with PREFIX\n");
+    fprintf(o, " --subalignments / -s FILE   Write the aligned paths of every subproblem to FILE (which must not exist yet)\n");
+    fprintf(o, " --cyclize / -c              Merge long tandem duplications into cycles of the final graph\n");
+    fprintf(o, " --cyclizing-size / -y INT   With -c, merge tandem duplications longer than INT bases [%s]\n", config_value(defaults, "min_cyclizing_length").c_str());
+    fprintf(o, " --max-count / -m INT        Use an anchor only if it occurs at most INT times [%s]\n", config_value(defaults, "max_count").c_str());
+    fprintf(o, " --max-anchors / -a INT      Consider at most INT anchors per merge [%s]\n", config_value(defaults, "max_num_match_pairs").c_str());
+    fprintf(o, " --count-power / -p FLOAT    Divide anchor weights by the count raised to FLOAT [%s]\n", config_value(defaults, "pair_count_power").c_str());
+    fprintf(o, " --chain-alg / -g INT        Chaining algorithm: 1 (sparse), 2 (sparse affine) [%s]\n", config_value(defaults, "chaining_algorithm").c_str());
+    fprintf(o, " --no-unaln / -u             Do not look for unalignable regions\n");
+    fprintf(o, " --verbosity / -v INT        0 (silent), 1 (minimal), 2 (basic), 3 (verbose), 4 (debug) [%s]\n", config_value(defaults, "logging_level").c_str());
+    fprintf(o, " --config / -C FILE          Take every parameter from this config file (overrides all other command line input)\n");
+    fprintf(o, " --generate-config / -G      Write a config file with the current parameters to standard output and exit\n");
+    fprintf(o, " --restart / -R              Resume an interrupted run (the first run needs -S)\n");
+    fprintf(o, " --threads / -t INT          Worker contexts that run calibrations and independent merges side by side [%s]\n", config_value(defaults, "threads").c_str());
+    fprintf(o, " --skip-calibration          Keep the starting score scale instead of calibrating it to the input\n");
+    fprintf(o, " --force-gfa-output          Write a GFA even for two sequences\n");
+    fprintf(o, " --bond-prefix PREFIX        With -c, write the alignment of every tandem duplication found to files starting with PREFIX\n");
+    fprintf(o, " --devices LIST              Comma-separated GPU ordinals the worker contexts are spread over [the first GPU]\n");
+    fprintf(o, " --help / -h                 Print this message and exit\n");
+    fprintf(o, "\n");
+    fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
+    fprintf(o, "-t sets worker contexts; --devices is added; -v gates this tool's own progress lines. See README.md.\n");
+}
+
+struct Owned {
+    cl_config* cfg = nullptr;
+    cl_config* defaults = nullptr;
+    cl_context* ctx = nullptr;
+    ~Owned() {
+        if (ctx) cl_context_destroy(ctx);
+        cl_config_free(cfg);
+        cl_config_free(defaults);
+    }
+};
+
+int run(int argc, char** argv) {
+    Owned own;
+    own.cfg = cl_config_default();
+    own.defaults = cl_config_default();
+    if (!own.cfg || !own.defaults) return fail("out of memory");
+    cl_config* cfg = own.cfg;
+
+    std::string config_name;
+    bool force_gfa_output = false, generate_config = false;
+    std::vector<int> devices;
+
+    enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004 };
+    static const struct option options[] = {
+        {"tree", required_argument, nullptr, 'T'},
+        {"all-pairs", required_argument, nullptr, 'A'},
+        {"all-subprobs", required_argument, nullptr, 'S'},
+        {"subalignments", required_argument, nullptr, 's'},
+        {"cyclize", no_argument, nullptr, 'c'},
+        {"cyclizing-size", required_argument, nullptr, 'y'},
+        {"max-count", required_argument, nullptr, 'm'},
+        {"max-anchors", required_argument, nullptr, 'a'},
+        {"count-power", required_argument, nullptr, 'p'},
+        {"chain-alg", required_argument, nullptr, 'g'},
+        {"no-unaln", no_argument, nullptr, 'u'},
+        {"verbosity", required_argument, nullptr, 'v'},
+        {"config", required_argument, nullptr, 'C'},
+        {"generate-config", no_argument, nullptr, 'G'},
+        {"restart", no_argument, nullptr, 'R'},
+        {"threads", required_argument, nullptr, 't'},
+        {"help", no_argument, nullptr, 'h'},
+        {"skip-calibration", no_argument, nullptr, OPT_SKIP_CALIBRATION},
+        {"force-gfa-output", no_argument, nullptr, OPT_FORCE_GFA_OUTPUT},
+        {"bond-prefix", required_argument, nullptr, OPT_BOND_PREFIX},
+        {"devices", required_argument, nullptr, OPT_DEVICES},
+        {nullptr, 0, nullptr, 0},
+    };
+    opterr = 0;   // reported here, as "error: ..."
+    while (true) {
+        const int o = getopt_long(argc, argv, ":T:A:S:s:cy:m:a:p:g:uv:C:GRt:h", options, nullptr);
+        if (o == -1) break;
+        const char* name = nullptr;   // the parameter this option sets from its argument
+        const char* value = optarg;
+        switch (o) {
+        case 'T': name = "tree_name"; break;
+        case 'A': name = "all_pairs_prefix"; break;
+        case 'S': name = "subproblems_prefix"; break;
+        case 's': name = "subalignments_filepath"; break;
+        case 'c': name = "cyclize_tandem_duplications"; value = "true"; break;
+        case 'y': name = "min_cyclizing_length"; break;
+        case 'm': name = "max_count"; break;
+        case 'a': name = "max_num_match_pairs"; break;
+        case 'p': name = "pair_count_power"; break;
+        case 'g': name = "chaining_algorithm"; break;
+        case 'u': name = "constraint_method"; value = "0"; break;
+        case 'v': name = "logging_level"; break;
+        case 'C': config_name = optarg; break;
+        case 'G': generate_config = true; break;
+        case 'R': name = "restart"; value = "true"; break;
+        case 't': name = "threads"; break;
+        case 'h': print_help(own.defaults); return 0;
+        case OPT_SKIP_CALIBRATION: name = "skip_calibration"; value = "true"; break;
+        case OPT_FORCE_GFA_OUTPUT: force_gfa_output = true; break;
+        case OPT_BOND_PREFIX: name = "bonds_prefix"; break;
+        case OPT_DEVICES:
+            if (!parse_devices(optarg, devices)) return fail(std::string("--devices expects comma-separated device ordinals, got '") + optarg + "'");
+            break;
+        case ':':
+        default: {
+            // optopt names a short option; a long one is the argument getopt just stepped over
+            const std::string opt = optopt > 0 && optopt < 128 ? std::string("-") + (char)optopt : std::string(optind > 0 && optind <= argc ? argv[optind - 1] : "");
+            fprintf(stderr, o == ':' ? "error: option '%s' requires an argument\n" : "error: unknown option '%s'\n", opt.c_str());
+            print_help(own.defaults);
+            return 1;
+        }
+        }
+        if (name && cl_config_set(cfg, name, value)) return fail(lib_error());
+    }
+
+    const int n_positional = argc - optind;
+    if (n_positional > 1) {
+        fprintf(stderr, "error: expected between 0 and 1 positional arguments but got %d\n", n_positional);
+        print_help(own.defaults);
+        return 1;
+    }
+    if (n_positional == 1 && cl_config_set(cfg, "fasta_name", argv[optind])) return fail(lib_error());
+
+    if (generate_config) {
+        const std::string text = generate(cfg);
+        fwrite(text.data(), 1, text.size(), stdout);
+        return fflush(stdout) == 0 ? 0 : fail("could not write the config to standard output");
+    }
+
+    if (!config_name.empty()) {
+        if (generate(cfg) != generate(own.defaults))
+            fprintf(stderr, "warning: All other command-line arguments are being overridden by config file parameters.\n\n");
+        std::string text, err;
+        if (!read_input(config_name, text, err)) return fail(err);
+        cl_config* parsed = nullptr;
+        if (cl_config_parse(text.data(), text.size(), &parsed)) return fail(lib_error());
+        cl_config_free(own.cfg);
+        cfg = own.cfg = parsed;
+    }
+
+    if (cl_config_validate(cfg)) {
+        fprintf(stderr, "error: %s\n", lib_error().c_str());
+        print_help(own.defaults);
+        return 1;
+    }
+    g_level = atoi(config_value(cfg, "logging_level").c_str());
+
+    {
+        std::string cmd = "Executing command:";
+        for (int i = 0; i < argc; ++i) cmd += std::string(" ") + argv[i];
+        log_line(LOG_MINIMAL, cmd);
+    }
+    log_line(LOG_DEBUG, "config file:\n\n" + generate(cfg) + "\n");
+
+    const std::string fasta_name = config_value(cfg, "fasta_name"), tree_name = config_value(cfg, "tree_name");
+    std::string fasta_text, newick, err;
+    if (!read_input(fasta_name, fasta_text, err)) return fail(err);
+    if (!tree_name.empty() && !read_input(tree_name, newick, err)) return fail(err);
+
+    log_line(LOG_BASIC, "Reading input.");
+    cl_fasta fa;
+    if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) return fail(lib_error());
+    const uint64_t n_sequences = fa.n_sequences;
+    cl_fasta_free(&fa);
+    if (n_sequences < 2)
+        return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains " + std::to_string(n_sequences) +
+                    " sequence(s), cannot form an alignment");
+    if (tree_name.empty() && n_sequences > 2)
+        fprintf(stderr, "warning: it is highly recommended to provide a guide tree (-T) when aligning > 2 sequences\n");
+
+    cl_msa_params mp;
+    if (cl_config_msa_params(cfg, &mp)) return fail(lib_error());
+    mp.force_gfa_output = force_gfa_output;
+    if (!devices.empty()) {
+        mp.devices = devices.data();
+        mp.n_devices = (int)devices.size();
+    }
+
+    // the device is opened only now: everything above works without one
+    const int device = devices.empty() ? 0 : devices[0];
+    log_line(LOG_VERBOSE, "Opening GPU " + std::to_string(device) + " with " + std::to_string(mp.n_workers) + " worker context(s).");
+    own.ctx = cl_context_create(device);
+    if (!own.ctx) return fail("no usable GPU: " + lib_error());
+
+    log_line(LOG_BASIC, "Aligning " + std::to_string(n_sequences) + " sequences.");
+    char* text = nullptr;
+    uint64_t len = 0;
+    cl_msa_stats st;
+    memset(&st, 0, sizeof(st));
+    if (cl_msa(own.ctx, fasta_text.data(), fasta_text.size(), tree_name.empty() ? nullptr : newick.c_str(), &mp, &text, &len, &st)) {
+        const char* e = cl_last_error(own.ctx);
+        return fail(e && *e ? e : lib_error());
+    }
+    const bool written = fwrite(text, 1, len, stdout) == len && fflush(stdout) == 0;
+    free(text);
+    if (!written) return fail("could not write the alignment to standard output");
+
+    char line[512];
+    snprintf(line, sizeof(line), "%llu merges, score scale %.6g: calibration %.2f s, matches %.2f s, alignment %.2f s, fusion %.2f s",
+             (unsigned long long)st.n_merges, st.score_scale, st.calibration_s, st.match_s, st.align_s, st.fuse_s);
+    log_line(LOG_VERBOSE, line);
+    if (st.n_restarted) log_line(LOG_BASIC, "Loaded " + std::to_string(st.n_restarted) + " subproblem(s) from an earlier run.");
+    if (mp.cyclize) log_line(LOG_BASIC, "Merged " + std::to_string(st.n_bonds) + " tandem duplication(s), realigned " + std::to_string(st.n_polished_regions) + " region(s).");
+    snprintf(line, sizeof(line), "Run completed successfully in %.2f s, exiting.", st.total_s);
+    log_line(LOG_MINIMAL, line);
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    try {
+        return run(argc, argv);
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    } catch (...) {
+        return fail("unexpected failure");
+    }
+}

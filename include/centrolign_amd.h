@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 13   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 14   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -859,6 +859,33 @@ typedef struct cl_msa_stats {
 } cl_msa_stats;
 int  cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const char* newick /* NULL: in-order tree */,
             const cl_msa_params* params, char** text_out, uint64_t* len_out, cl_msa_stats* stats /* may be NULL */);
+
+/* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
+ * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
+ * from.  Enums are integers.  Parameters are named as in the reference; a value is given and read back as config text (the same parsers
+ * a config file goes through: integers whole, booleans true/false/T/F/1/0 in the reference's spellings, arrays as three comma-separated
+ * numbers).  Host only, no device needed.  Errors: CL_ERR_INVALID_ARGUMENT, message via cl_last_error(NULL).
+ * cl_config_parse:    Parameters(std::istream&) (:219-313): the defaults, then every "name: value" line after the first "---"; '#'
+ *                     starts a comment; double quotes around a value are dropped.  A line without ':', an unknown name or a value of the
+ *                     wrong type is an error.
+ * cl_config_generate: generate_config (:335-359): the same keys, order, layout and quoting (comments in this project's words).  Doubles are
+ *                     written as a default-formatted C++ stream writes them (6 significant digits) unless that loses the value; then with
+ *                     as many more digits as it takes to read back the same number.
+ * cl_config_validate: validate (:362-463): the same bounds, the same meaning of every message.
+ * cl_config_msa_params: apply (:112-194) onto cl_msa_params_default: the numeric bounds of cl_config_validate are checked first (the FASTA
+ *                     name is not).  String fields point into cfg and live as long as it does; empty strings become NULL.  threads ->
+ *                     n_workers; force_gfa_output, devices and n_devices stay as cl_msa_params_default leaves them (they are not parameters).
+ *                     memory_restraint_size, use_color_set_size and preserve_subproblems change no output (see README.md).
+ * Text returned through char** is malloc'ed: release it with free(). */
+typedef struct cl_config cl_config;
+cl_config* cl_config_default(void);   /* NULL only when out of memory */
+void       cl_config_free(cl_config* cfg);
+int        cl_config_set(cl_config* cfg, const char* name, const char* text);
+int        cl_config_get(const cl_config* cfg, const char* name, char** text_out);
+int        cl_config_parse(const char* text, uint64_t len, cl_config** out);
+int        cl_config_generate(const cl_config* cfg, char** text_out, uint64_t* len_out /* may be NULL */);
+int        cl_config_validate(const cl_config* cfg);
+int        cl_config_msa_params(const cl_config* cfg, cl_msa_params* out);
 
 #ifdef __cplusplus
 }
