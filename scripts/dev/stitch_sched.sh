@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 run() {
   lay=$1; shift
-  env "$@" python bench.py --no-extras --no-cpu-baseline --steps 30 --warmup 5 --plans $lay 2>/dev/null | python -c "
+  env "$@" python bench.py --full --no-extras --no-cpu-baseline --steps 30 --warmup 5 --plans $lay 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-5s %-50s ms/step %.3f  value %.3g  other layout %.3f' % ('$lay', '$*', d['ms_per_step'], d['value'], d['config']['other_plan_layout']['ms_per_step']))

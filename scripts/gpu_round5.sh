@@ -14,10 +14,10 @@ cp gpurun_out/dom/dominant_launches.json profiles/dominant_launches_latest.json 
 cp gpurun_out/dom/dominant_launches.json $OUT/dominant_launches.json 2>/dev/null
 cp gpurun_out/dom/trace/*kernel_stats.csv $OUT/step_kernel_stats.csv 2>/dev/null
 rm -rf gpurun_out/dom/pmc_FETCH_SIZE gpurun_out/dom/pmc_WRITE_SIZE gpurun_out/dom/trace
-timeout 900 python bench.py 2>$OUT/bench.err | tee $OUT/bench.json | cut -c1-600
+timeout 900 python bench.py --full 2>$OUT/bench.err | tee $OUT/bench.json | cut -c1-600
 export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o r05 -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_prof.json 2>$OUT/prof.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o r05 -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_prof.json 2>$OUT/prof.err
 cd $R
 cp $OUT/prof/*kernel_stats.csv $OUT/c3_msa_kernel_stats.csv 2>/dev/null; rm -rf $OUT/prof
 timeout 300 python scripts/stress_set.py --json $OUT/stress_set.json > $OUT/stress.txt 2>&1; cat $OUT/stress.txt | cut -c1-200

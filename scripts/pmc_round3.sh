@@ -10,7 +10,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-extras --workers 1"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --workers 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o r03 -- python3 $R/bench.py $ARGS > $OUT/prof_bench.json 2>$OUT/prof_bench.err
 rm -f $OUT/prof_bench/r03_kernel_trace.csv
 for c in FETCH_SIZE WRITE_SIZE; do

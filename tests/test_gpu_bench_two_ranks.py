@@ -20,7 +20,7 @@ def run_bench(extra, env_extra=None, timeout=900):
 
 @pytest.mark.gpu
 def test_bench_with_two_ranks_on_one_device():
-    r = run_bench([])
+    r = run_bench(["--full"])          # (the stealing pass, the five blocks and the roofline are --full measurements)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
