@@ -804,6 +804,82 @@ def msa_plan(newick, names):
         lib.cl_msa_plan_free(C.byref(p))
 
 
+class KmerDistancesC(C.Structure):
+    """cl_kmer_distances"""
+    _fields_ = [("n", C.c_uint64), ("k", C.c_int), ("total", C.POINTER(C.c_uint64)), ("shared", C.POINTER(C.c_uint64)),
+                ("distance", C.POINTER(C.c_double)), ("spectra_ms", C.c_float), ("pairs_ms", C.c_float)]
+
+
+def _ctx_handle(ctx):
+    return ctx.handle if isinstance(ctx, Context) else ctx
+
+
+def _raise_last(lib, rc, handle=None):
+    msg = lib.cl_last_error(handle)
+    raise ClError(rc, msg.decode() if msg else "")
+
+
+def kmer_distances(ctx, sequences, k=21, want_times=False):
+    """cl_kmer_distances_compute on the device: (total [n] uint64, shared [n, n] uint64, distance [n, n] float64) of the exact forward-strand
+    k-mer spectra of `sequences` (str or bytes); with want_times=True a fourth item {"spectra_ms", "pairs_ms"} (device time by events)"""
+    lib = load_library()
+    h = _ctx_handle(ctx)
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+    n = len(raw)
+    bufs = (C.c_char_p * max(n, 1))(*raw)
+    lens = np.array([len(s) for s in raw], dtype=np.uint64)
+    lib.cl_kmer_distances_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(KmerDistancesC)]
+    lib.cl_kmer_distances_free.argtypes = [C.POINTER(KmerDistancesC)]
+    lib.cl_kmer_distances_free.restype = None
+    out = KmerDistancesC()
+    rc = lib.cl_kmer_distances_compute(h, bufs, lens.ctypes.data, n, int(k), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        total = np.ctypeslib.as_array(out.total, shape=(n,)).copy()
+        shared = np.ctypeslib.as_array(out.shared, shape=(n * n,)).copy().reshape(n, n)
+        distance = np.ctypeslib.as_array(out.distance, shape=(n * n,)).copy().reshape(n, n)
+        times = {"spectra_ms": float(out.spectra_ms), "pairs_ms": float(out.pairs_ms)}
+    finally:
+        lib.cl_kmer_distances_free(C.byref(out))
+    return (total, shared, distance, times) if want_times else (total, shared, distance)
+
+
+def neighbor_joining_newick(distance, names):
+    """cl_neighbor_joining_newick (host only): the midpoint-rooted neighbor-joining tree of an [n, n] distance matrix as Newick text"""
+    lib = load_library()
+    d = np.ascontiguousarray(distance, dtype=np.float64)
+    n = len(names)
+    if d.shape != (n, n):
+        raise ValueError("distance must be [%d, %d], got %s" % (n, n, d.shape))
+    arr = (C.c_char_p * max(n, 1))(*[nm.encode() for nm in names])
+    lib.cl_neighbor_joining_newick.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = lib.cl_neighbor_joining_newick(d.ctypes.data, n, arr, C.byref(text), C.byref(ln))
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return C.string_at(text.value, ln.value).decode()
+    finally:
+        _libc_free(text)
+
+
+def infer_guide_tree(ctx, fasta_text, k=21):
+    """cl_infer_guide_tree: the Newick guide tree of a FASTA text from its k-mer distances (what the CLI's --infer-tree passes on)"""
+    lib = load_library()
+    h = _ctx_handle(ctx)
+    raw = fasta_text.encode() if isinstance(fasta_text, str) else bytes(fasta_text)
+    lib.cl_infer_guide_tree.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = lib.cl_infer_guide_tree(h, raw, len(raw), int(k), C.byref(text), C.byref(ln))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        return C.string_at(text.value, ln.value).decode()
+    finally:
+        _libc_free(text)
+
+
 def default_chain_params(global_anchoring=True):
     """the CLI's anchoring parameters (src/parameters.cpp:39-60)"""
     p = ChainParams()
@@ -1093,7 +1169,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 14    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 15    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1307,6 +1383,7 @@ EXPORTED_SYMBOLS = [
     "cl_polish_cyclized_graph",
     "cl_config_default", "cl_config_free", "cl_config_set", "cl_config_get", "cl_config_parse", "cl_config_generate", "cl_config_validate",
     "cl_config_msa_params",
+    "cl_kmer_distances_compute", "cl_kmer_distances_free", "cl_neighbor_joining_newick", "cl_infer_guide_tree",
 ]
 
 

@@ -4,10 +4,13 @@
 //   - every failure is "error: <message>" on stderr and exit status 1 (the reference lets some exceptions escape and aborts);
 //   - -p takes a decimal number (the reference stores an integer into a Double parameter, which its type check refuses: it aborts);
 //   - -t N runs N worker contexts; --devices LIST places them (cl_msa_params.devices);
+//   - --infer-tree infers the guide tree from k-mer distances (cl_infer_guide_tree) where the reference needs one from outside; --tree-out
+//     writes it;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
 #include <cerrno>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -114,10 +117,12 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --force-gfa-output          Write a GFA even for two sequences\n");
     fprintf(o, " --bond-prefix PREFIX        With -c, write the alignment of every tandem duplication found to files starting with PREFIX\n");
     fprintf(o, " --devices LIST              Comma-separated GPU ordinals the worker contexts are spread over [the first GPU]\n");
+    fprintf(o, " --infer-tree                Infer the guide tree from k-mer distances (k = 21, neighbor joining) instead of taking one\n");
+    fprintf(o, " --tree-out FILE             With --infer-tree, write the inferred Newick tree to FILE\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
-    fprintf(o, "-t sets worker contexts; --devices is added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "-t sets worker contexts; --devices, --infer-tree and --tree-out are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -139,10 +144,11 @@ int run(int argc, char** argv) {
     cl_config* cfg = own.cfg;
 
     std::string config_name;
-    bool force_gfa_output = false, generate_config = false;
+    std::string tree_out;
+    bool force_gfa_output = false, generate_config = false, infer_tree = false;
     std::vector<int> devices;
 
-    enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004 };
+    enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -165,6 +171,8 @@ int run(int argc, char** argv) {
         {"force-gfa-output", no_argument, nullptr, OPT_FORCE_GFA_OUTPUT},
         {"bond-prefix", required_argument, nullptr, OPT_BOND_PREFIX},
         {"devices", required_argument, nullptr, OPT_DEVICES},
+        {"infer-tree", no_argument, nullptr, OPT_INFER_TREE},
+        {"tree-out", required_argument, nullptr, OPT_TREE_OUT},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -197,6 +205,8 @@ int run(int argc, char** argv) {
         case OPT_DEVICES:
             if (!parse_devices(optarg, devices)) return fail(std::string("--devices expects comma-separated device ordinals, got '") + optarg + "'");
             break;
+        case OPT_INFER_TREE: infer_tree = true; break;
+        case OPT_TREE_OUT: tree_out = optarg; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -234,6 +244,10 @@ int run(int argc, char** argv) {
         cfg = own.cfg = parsed;
     }
 
+    // the tree options of this project, checked before anything is read or opened
+    if (infer_tree && !config_value(cfg, "tree_name").empty()) return fail("--infer-tree cannot be combined with a guide tree (-T or tree_name)");
+    if (!tree_out.empty() && !infer_tree) return fail("--tree-out needs --infer-tree");
+
     if (cl_config_validate(cfg)) {
         fprintf(stderr, "error: %s\n", lib_error().c_str());
         print_help(own.defaults);
@@ -261,7 +275,7 @@ int run(int argc, char** argv) {
     if (n_sequences < 2)
         return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains " + std::to_string(n_sequences) +
                     " sequence(s), cannot form an alignment");
-    if (tree_name.empty() && n_sequences > 2)
+    if (tree_name.empty() && !infer_tree && n_sequences > 2)
         fprintf(stderr, "warning: it is highly recommended to provide a guide tree (-T) when aligning > 2 sequences\n");
 
     cl_msa_params mp;
@@ -278,12 +292,35 @@ int run(int argc, char** argv) {
     own.ctx = cl_context_create(device);
     if (!own.ctx) return fail("no usable GPU: " + lib_error());
 
+    if (infer_tree) {   // the tree goes to cl_msa exactly as the text of a -T file would
+        log_line(LOG_BASIC, "Inferring a guide tree from k-mer distances.");
+        const auto t0 = std::chrono::steady_clock::now();
+        char* tree = nullptr;
+        uint64_t tree_len = 0;
+        if (cl_infer_guide_tree(own.ctx, fasta_text.data(), fasta_text.size(), 21, &tree, &tree_len)) {
+            const char* e = cl_last_error(own.ctx);
+            return fail(e && *e ? e : lib_error());
+        }
+        newick.assign(tree, tree_len);
+        free(tree);
+        char line[128];
+        snprintf(line, sizeof(line), "Inferred the guide tree in %.3f s.", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        log_line(LOG_VERBOSE, line);
+        log_line(LOG_DEBUG, "guide tree: " + newick);
+        if (!tree_out.empty()) {
+            FILE* f = fopen(tree_out.c_str(), "wb");
+            const std::string text = newick + "\n";
+            const bool written = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+            if ((f && fclose(f) != 0) || !written) return fail("could not write the guide tree to " + tree_out);
+        }
+    }
+
     log_line(LOG_BASIC, "Aligning " + std::to_string(n_sequences) + " sequences.");
     char* text = nullptr;
     uint64_t len = 0;
     cl_msa_stats st;
     memset(&st, 0, sizeof(st));
-    if (cl_msa(own.ctx, fasta_text.data(), fasta_text.size(), tree_name.empty() ? nullptr : newick.c_str(), &mp, &text, &len, &st)) {
+    if (cl_msa(own.ctx, fasta_text.data(), fasta_text.size(), tree_name.empty() && !infer_tree ? nullptr : newick.c_str(), &mp, &text, &len, &st)) {
         const char* e = cl_last_error(own.ctx);
         return fail(e && *e ? e : lib_error());
     }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 14   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 15   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -859,6 +859,32 @@ typedef struct cl_msa_stats {
 } cl_msa_stats;
 int  cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const char* newick /* NULL: in-order tree */,
             const cl_msa_params* params, char** text_out, uint64_t* len_out, cl_msa_stats* stats /* may be NULL */);
+
+/* --- a guide tree from the sequences (the CLI's --infer-tree; the reference has none: README, "Guide trees must be generated externally") --------
+ * cl_kmer_distances_compute: exact forward-strand k-mer count spectra on the device (tree_kernels.hip).  A k-mer is a window of k characters,
+ *   all from ACGTacgt (encode_base codes 0-3, src/utility.cpp:324-345); a window holding any other character is none.  total[i] = k-mers of
+ *   sequence i, shared[i][j] = sum over keys x of min(c_i(x), c_j(x)) in 64-bit integers (shared[i][i] = total[i]), and with the weighted
+ *   Jaccard J = shared / (total_i + total_j - shared) (0 for an empty union): distance = 1 when J = 0, +0 when J = 1, otherwise
+ *   min(1, -log(2J / (1 + J)) / k) (the Mash transform); the diagonal is 0.  k in 1..31, n >= 2.  spectra_ms / pairs_ms: device time of the
+ *   two phases by events.  The arrays are malloc'ed: release them with cl_kmer_distances_free.
+ * cl_neighbor_joining_newick: host only.  Neighbor joining (Saitou-Nei, Studier-Keppler Q; first strict minimum in list order; new nodes
+ *   appended; lengths that are not > 0 become +0), the midpoint of the longest leaf-to-leaf path (smallest (p, q) on a tie) as the root, and the
+ *   Newick text in the style of Tree::to_newick (src/tree.cpp:615-645): quoted leaf labels, ":%g" lengths on every non-root node, children in
+ *   the order of their smallest FASTA index, ";" and no line end.  The distance matrix must be finite and symmetric with a zero diagonal;
+ *   names must be distinct, non-empty and free of '"'.
+ * cl_infer_guide_tree: cl_parse_fasta, cl_kmer_distances_compute, cl_neighbor_joining_newick.  Text returned through char** is malloc'ed. */
+typedef struct cl_kmer_distances {
+    uint64_t  n;
+    int       k;
+    uint64_t* total;      /* [n] */
+    uint64_t* shared;     /* [n*n], symmetric, diagonal = total */
+    double*   distance;   /* [n*n] */
+    float     spectra_ms, pairs_ms;   /* device time by events */
+} cl_kmer_distances;
+int  cl_kmer_distances_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, int k, cl_kmer_distances* out);
+void cl_kmer_distances_free(cl_kmer_distances* d);
+int  cl_neighbor_joining_newick(const double* distance, uint64_t n, const char* const* names, char** newick_out, uint64_t* len_out /* may be NULL */);
+int  cl_infer_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, int k, char** newick_out, uint64_t* len_out /* may be NULL */);
 
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
