@@ -1030,9 +1030,24 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
     int rc;
     if ((rc = validate_side(ctx, batch->side[0], n, 1)) || (rc = validate_side(ctx, batch->side[1], n, 2))) return rc;
     const cl_align_params& ap = params->alignment_params;
-    if (ap.match > (1u << 20) || ap.mismatch > (1u << 20)) { set_error(ctx, "match/mismatch too large"); return CL_ERR_INVALID_ARGUMENT; }
-    for (int k = 0; k < 3; ++k)
-        if (ap.gap_open[k] > (1u << 24) || ap.gap_extend[k] > (1u << 24)) { set_error(ctx, "gap penalties too large"); return CL_ERR_INVALID_ARGUMENT; }
+    // Magnitudes beyond the fixed limits are taken where the batch keeps every score inside the int32 budget the reference has too:
+    // (n1 + n2 + 2) x (largest term) < 2^28 for its largest pair, so that nothing added to CL_NEG_INF (-2^30) wraps
+    bool small = ap.match <= (1u << 20) && ap.mismatch <= (1u << 20);
+    uint64_t term = std::max<uint64_t>(ap.match, ap.mismatch);
+    for (int k = 0; k < 3; ++k) {
+        small = small && ap.gap_open[k] <= (1u << 24) && ap.gap_extend[k] <= (1u << 24);
+        term = std::max<uint64_t>(term, (uint64_t)ap.gap_open[k] + ap.gap_extend[k]);
+    }
+    if (!small) {
+        uint64_t longest = 0;
+        for (uint64_t k = 0; k < n; ++k)
+            longest = std::max<uint64_t>(longest, (batch->side[0].node_off[k + 1] - batch->side[0].node_off[k]) + (batch->side[1].node_off[k + 1] - batch->side[1].node_off[k]));
+        if (term >= (1ull << 28) || longest >= (1ull << 28) || (longest + 2) * term >= (1ull << 28)) {
+            set_error(ctx, "%s: beyond 2^20 (match, mismatch) / 2^24 (gaps) a batch must keep (n1 + n2 + 2) x largest term below 2^28 for its largest pair",
+                      ap.match > (1u << 20) || ap.mismatch > (1u << 20) ? "match/mismatch too large" : "gap penalties too large");
+            return CL_ERR_INVALID_ARGUMENT;
+        }
+    }
 
     static const bool timing = getenv("CL_STITCH_TIMING") != nullptr;
     auto tp = std::chrono::steady_clock::now();

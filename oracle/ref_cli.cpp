@@ -5,12 +5,15 @@
  * src/core.cpp:370-422); tests/golden/make_c3_digests.py turns those files into the digests the -m gpu suite reproduces.
  *
  *   ref_cli FASTA NEWICK|- PREFIX|- OUT|- [max_num_match_pairs] [verbosity] [restart 0|1] [overrides]
- *   overrides: typed settings of the reference's Parameters, "b:cyclize_tandem_duplications=1;i:min_cyclizing_length=5000;d:name=0.2"
+ *   overrides: typed settings of the reference's Parameters, "b:cyclize_tandem_duplications=1;i:min_cyclizing_length=5000;d:name=0.2";
+ *              "c:config=FILE" starts from a config file read by the reference's own Parameters reader (the way to array-typed settings
+ *              such as stitch_gap_open); the other overrides and the positional arguments are applied on top of it
  */
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -34,7 +37,19 @@ int main(int argc, char** argv) {
     int verbosity = argc > 6 ? atoi(argv[6]) : 2;
     bool restart = argc > 7 && atoi(argv[7]) != 0;
     try {
-        Parameters params;
+        std::unique_ptr<Parameters> from_file;
+        if (argc > 8) {
+            const std::string all = argv[8];
+            const size_t at = all.find("c:config=");
+            if (at != std::string::npos && (at == 0 || all[at - 1] == ';')) {
+                const std::string path = all.substr(at + 9, all.find(';', at) == std::string::npos ? std::string::npos : all.find(';', at) - at - 9);
+                std::ifstream cfg(path);
+                if (!cfg) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
+                from_file.reset(new Parameters(cfg));
+            }
+        }
+        Parameters defaults;
+        Parameters& params = from_file ? *from_file : defaults;
         params.set<std::string>("fasta_name", fasta);
         if (prefix != "-") params.set<std::string>("subproblems_prefix", prefix);
         if (budget > 0) params.set<int64_t>("max_num_match_pairs", (int64_t)budget);
@@ -46,6 +61,7 @@ int main(int argc, char** argv) {
                 const size_t eq = item.find('=');
                 if (item.size() < 4 || item[1] != ':' || eq == std::string::npos) continue;
                 const std::string name = item.substr(2, eq - 2), val = item.substr(eq + 1);
+                if (item[0] == 'c') continue;
                 if (item[0] == 'b') params.set<bool>(name, val != "0");
                 else if (item[0] == 'i') params.set<int64_t>(name, (int64_t)atoll(val.c_str()));
                 else if (item[0] == 'd') params.set<double>(name, atof(val.c_str()));

@@ -3,7 +3,10 @@
           forks (strips), NumPW as the library picks it or forced 1 / 2 / 3 — aligned pairs, scores, routes against oracle/popoa_oracle.c;
   chain : two multi-path graphs out of the library's own merges of random HOR sequences, a random subset of their match sets, the affine and the gap-free DP, local and
           global anchoring, random scale — DP values as bit patterns and the chain against oracle/chain_oracle.cpp.
-usage: python3 scripts/fuzz_gpu.py [--seconds T] [--seed S] [--what stitch,chain] [--json OUT]; exit code 1 on any mismatch (each printed with its seed)"""
+Scoring parameters are drawn per case from the generator of the test suite's random_* sets (tests/helpers.py: draw_stitch_values, draw_chain_params; the draw's seed is
+printed with a mismatch; a stitch draw outside the reference's int32 domain for its batch is drawn again; one that leaves Stitcher::subalign's NumPW choice undefined runs
+with NumPW given); --default-params keeps the CLI defaults throughout.
+usage: python3 scripts/fuzz_gpu.py [--seconds T] [--seed S] [--what stitch,chain] [--default-params] [--json OUT]; exit code 1 on any mismatch (each printed with its seed)"""
 import argparse
 import collections
 import json
@@ -17,6 +20,24 @@ import numpy as np  # noqa: E402
 
 from centrolign_amd import capi, synth  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
+from tests import helpers as H  # noqa: E402
+
+DEFAULT_PARAMS = False
+
+
+def draw_stitch_params(rng, b):
+    """(StitchParams, seed of the draw or -1 for the defaults)"""
+    if DEFAULT_PARAMS:
+        return capi.default_stitch_params(), -1
+    for _ in range(50):
+        pseed = int(rng.integers(0, 1 << 30))
+        p = H._stitch_params_from(*H.draw_stitch_values(pseed))
+        try:
+            H.check_stitch_domain(b, p)
+        except AssertionError:
+            continue
+        return p, pseed
+    return capi.default_stitch_params(), -1
 
 
 def stitch_case(rng):
@@ -56,24 +77,29 @@ def stitch_case(rng):
 
 
 def fuzz_stitch(ctx, rng, seconds, log):
-    seen, n, bad, cells = collections.Counter(), 0, 0, 0
+    seen, n, bad, cells, defaults = collections.Counter(), 0, 0, 0, 0
     t_end = time.time() + seconds
     while time.time() < t_end:
         kind, seed, b, force, npw = stitch_case(rng)
-        plan = ctx.plan(b, force_num_pw=force)
+        params, pseed = draw_stitch_params(rng, b)
+        defaults += pseed < 0
+        if force is None and not H.subalign_defined(params):
+            npw = int(rng.integers(1, 4))
+            force = np.full(b.n_problems, npw, np.uint8)
+        plan = ctx.plan(b, params, force_num_pw=force)
         for li in plan.launches():
             seen[li["kernel"].split(" x ")[0]] += 1
         plan.execute(); plan.sync()
         got = plan.collect()
         cells += int(plan.stats()["dp_cells"])
         plan.destroy()
-        want = po.oracle_stitch_batch(b, force_num_pw=force)
+        want = po.oracle_stitch_batch(b, params, force_num_pw=force)
         diff = got.same_as(want)
         n += 1
         if diff is not None:
             bad += 1
-            log("MISMATCH stitch kind %s seed %d npw %d problems %d: %s" % (kind, seed, npw, b.n_problems, diff))
-    return dict(cases=n, mismatches=bad, dp_cells=cells, launches_by_kernel=dict(seen))
+            log("MISMATCH stitch kind %s seed %d params seed %d %s npw %d problems %d: %s" % (kind, seed, pseed, H.alignment_values(params), npw, b.n_problems, diff))
+    return dict(cases=n, mismatches=bad, dp_cells=cells, cases_at_default_params=int(defaults), launches_by_kernel=dict(seen))
 
 
 def relabelled(g, src_label, snk_label):
@@ -111,13 +137,15 @@ def fuzz_chain(ctx, rng, seconds, log):
         for algo in ("affine", "sparse"):
             glob = bool(rng.random() < 0.5)
             scale = float(rng.choice([1.0, 0.6, 0.05]))
-            kw = dict(want_dp=True, params=capi.default_chain_params(global_anchoring=glob))
+            pseed = -1 if DEFAULT_PARAMS else int(rng.integers(0, 1 << 30))
+            cp = capi.default_chain_params(global_anchoring=glob) if DEFAULT_PARAMS else H.draw_chain_params(pseed, global_anchoring=glob)
+            kw = dict(want_dp=True, params=cp)
             if algo == "affine":
                 got = ctx.chain_sparse_affine(g1, g2, ms, scale=scale, **kw)
-                want_chain, want_dp = po.oracle_chain("affine", g1, g2, ms, scale=scale, want_dp=True, global_anchoring=glob)
+                want_chain, want_dp = po.oracle_chain("affine", g1, g2, ms, scale=scale, params=cp, want_dp=True, global_anchoring=glob)
             else:
                 got = ctx.chain_sparse_affine(g1, g2, ms, sparse=True, **kw)
-                want_chain, want_dp = po.oracle_chain("sparse", g1, g2, ms, want_dp=True, global_anchoring=glob)
+                want_chain, want_dp = po.oracle_chain("sparse", g1, g2, ms, params=cp, want_dp=True, global_anchoring=glob)
             n += 1
             pairs += int(ms.n_pairs())
             shapes["%d x %d paths" % (n1, n2)] += 1
@@ -125,8 +153,8 @@ def fuzz_chain(ctx, rng, seconds, log):
             ok_chain = np.array_equal(got["chain"], want_chain)
             if not (ok_dp and ok_chain):
                 bad += 1
-                log("MISMATCH chain %s seed %d paths %d+%d length %d pairs %d global %d scale %g: dp %s chain %s" % (
-                    algo, seed, n1, n2, length, ms.n_pairs(), glob, scale, "same" if ok_dp else "DIFFERS", "same" if ok_chain else "DIFFERS"))
+                log("MISMATCH chain %s seed %d params seed %d paths %d+%d length %d pairs %d global %d scale %g: dp %s chain %s" % (
+                    algo, seed, pseed, n1, n2, length, ms.n_pairs(), glob, scale, "same" if ok_dp else "DIFFERS", "same" if ok_chain else "DIFFERS"))
     return dict(cases=n, mismatches=bad, match_pairs=pairs, cases_by_shape=dict(shapes))
 
 
@@ -136,7 +164,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--what", default="stitch,chain")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--default-params", action="store_true", help="the CLI's default scoring in every case (the campaign as it ran before the parameters were drawn)")
     args = ap.parse_args()
+    global DEFAULT_PARAMS
+    DEFAULT_PARAMS = args.default_params
     lines = []
 
     def log(s):

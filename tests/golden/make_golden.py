@@ -222,6 +222,46 @@ def msa_goldens():
     np.savez_compressed(os.path.join(HERE, "msa_text.npz"), **out)
 
 
+PARAMS_CASE_SETTINGS = (("stitch_match", "20", "3"), ("stitch_mismatch", "80", "4"), ("stitch_gap_open", "60,800,2500", "2,9,30"), ("stitch_gap_extend", "30,5,1", "5,2,1"),
+                        ("anchor_gap_open", "1.25,50,5000", "0,10,10"), ("anchor_gap_extend", "2.5,0.1,0.0015", "0.5,0.5,0"), ("anchor_score_function", "2", "1"),
+                        ("pair_count_power", "0.5", "0.75"))
+
+
+def msa_params_goldens():
+    # 14b. one end-to-end run away from the default scoring: msa4_8k of helpers.msa_cases() (4 x 8 kbp, seed 13, budget 20 000) by the compiled reference's own flow
+    #      (oracle/_ref/ref_cli) from a config file that its own Parameters reader reads: this project's `centrolign -G` output with the eight settings of
+    #      PARAMS_CASE_SETTINGS edited (params_msa4_8k.yaml, settings only; the test edits the inputs and the budget in).  Stored: the GFA and the -s subalignment text.
+    #      The reference accepts this config as it stands: no neighbouring config had to be chosen.  On this input its GFA and -s text come out the SAME bytes as
+    #      under the default scoring (checked here and printed): the arrays differ by substitutions and whole-repeat indels, the anchors are dense, and what is
+    #      left between them aligns the same way under both scorings.  The case pins that the library, too, is unmoved by the config; it is not a sensitive
+    #      probe of the scoring (tests/test_gpu_param_sweep.py is).
+    import gzip
+    import subprocess
+    import tempfile
+    from tests import helpers as H
+    from centrolign_amd import msa
+    root = os.path.dirname(os.path.dirname(HERE))
+    text = subprocess.check_output([os.path.join(root, "centrolign_amd", "bin", "centrolign"), "-G"]).decode()
+    for key, old, new in PARAMS_CASE_SETTINGS:
+        assert text.count(" %s: %s\n" % (key, old)) == 1, key
+        text = text.replace(" %s: %s\n" % (key, old), " %s: %s\n" % (key, new))
+    open(os.path.join(HERE, "params_msa4_8k.yaml"), "w").write(text)
+    name, n, length, seed, budget = [c for c in H.msa_cases() if c[0] == "msa4_8k"][0]
+    seqs = synth.hor_sequences(seed, length, n, seq_div=0.01, hor_div=0.03, indel_hor=2)
+    names = ["seq%d" % i for i in range(n)]
+    with tempfile.TemporaryDirectory() as d:
+        synth.write_fasta(os.path.join(d, "in.fa"), seqs, names)
+        open(os.path.join(d, "t.nwk"), "w").write(msa.newick(msa.balanced_tree(names)) + ";\n")
+        subprocess.check_call([os.path.join(root, "oracle", "_ref", "ref_cli"), "in.fa", "t.nwk", "-", "out.gfa", str(budget), "0", "0",
+                               "c:config=%s;s:subalignments_filepath=sub.txt" % os.path.join(HERE, "params_msa4_8k.yaml")], cwd=d)
+        gfa, sub = open(os.path.join(d, "out.gfa"), "rb").read(), open(os.path.join(d, "sub.txt"), "rb").read()
+    for fname, data in (("params_msa4_8k.gfa.gz", gfa), ("params_msa4_8k.sub.txt.gz", sub)):
+        with open(os.path.join(HERE, fname), "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", mtime=0, filename="") as g:
+            g.write(data)
+    default = bytes(np.load(os.path.join(HERE, "msa_text.npz"))["msa4_8k"])
+    print("msa4_8k_params: GFA %d bytes (%s the default-scoring GFA), -s text %d bytes" % (len(gfa), "differs from" if gfa != default else "equals", len(sub)))
+
+
 def msa_big_goldens():
     # 15. two larger end-to-end fixtures from the reference's own CLI flow (oracle/_ref/ref_cli, -S for the subproblems):
     #     BASELINE configs[0] — the pairwise 2 x 20 kbp pair, seed 1, default budget (the reference's CPU-runnable case, ~2 min) —
@@ -333,6 +373,8 @@ def main():
         return exhaustive_goldens()
     if len(sys.argv) > 1 and sys.argv[1] == "msa_big":
         return msa_big_goldens()
+    if len(sys.argv) > 1 and sys.argv[1] == "msa_params":
+        return msa_params_goldens()
     if len(sys.argv) > 1 and sys.argv[1] == "msa":
         return msa_goldens()
     if len(sys.argv) > 1 and sys.argv[1] == "io":

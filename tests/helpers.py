@@ -261,3 +261,192 @@ def msa_cases():
     """(name, n sequences, length, seed, max_num_match_pairs) of the end-to-end fixtures (balanced guide tree over seq0..)"""
     return [("pair_10k", 2, 10000, 21, 1250000), ("pair_60k", 2, 60000, 3, 100000), ("msa4_8k", 4, 8000, 13, 20000), ("msa3_6k", 3, 6000, 5, 1250000),
             ("msa5_5k", 5, 5000, 8, 8000)]
+
+
+# the parameter points of the scoring sweep ------------------------------------------------------------------
+# (tests/test_param_sweep.py, tests/test_gpu_param_sweep.py, tests/golden/make_param_sweep.py, scripts/fuzz_gpu.py)
+# name -> (match, mismatch, gap_open, gap_extend); every set is valid under cl_config_validate
+STITCH_SETS = {
+    "edit": (0, 1, (0, 0, 0), (1, 1, 1)),                        # match 0; three identical pieces; zero opens
+    "free_gaps": (1, 1, (0, 0, 0), (0, 0, 0)),                   # every gap free: the boundary closed forms are all 0
+    "free_mismatch": (5, 0, (60, 800, 2500), (30, 5, 1)),        # mismatch 0
+    "equal_pieces": (20, 80, (7, 7, 7), (3, 3, 3)),              # piece ties with non-zero costs
+    "near_crossovers": (3, 4, (2, 9, 30), (5, 2, 1)),            # crossovers at gap lengths 3 and 21
+    "flat_tail": (20, 80, (60, 800, 2500), (30, 5, 0)),          # zero extend on the last piece only
+}
+RANDOM_STITCH_SEEDS = tuple(range(12))
+STITCH_DRAW_VALUES = (0, 1, 2, 3, 5, 20, 100, 1000)
+STITCH_SET_NAMES = tuple(STITCH_SETS) + ("large",) + tuple("random_%d" % s for s in RANDOM_STITCH_SEEDS)
+STITCH_SCORE_BUDGET = 1 << 28      # the reference computes in int32_t: (n1 + n2 + 2) * (largest term) must stay below this
+LARGE_TERM_FLOOR = 1 << 20
+
+
+def draw_stitch_values(seed):
+    """(match, mismatch, gap_open, gap_extend) of random_<seed>: every field drawn from STITCH_DRAW_VALUES, opens sorted upwards, extends downwards"""
+    rng = np.random.default_rng(7700 + seed)
+    v = rng.choice(STITCH_DRAW_VALUES, 8)
+    return int(v[0]), int(v[1]), tuple(sorted(int(x) for x in v[2:5])), tuple(sorted((int(x) for x in v[5:8]), reverse=True))
+
+
+def _stitch_params_from(match, mismatch, gap_open, gap_extend):
+    p = capi.default_stitch_params()
+    p.alignment_params = capi.make_align_params(match, mismatch, list(gap_open), list(gap_extend))
+    return p
+
+
+def largest_pair(batch):
+    n1, n2 = batch.sizes()
+    return int((n1.astype(np.int64) + n2.astype(np.int64)).max()) if batch.n_problems else 0
+
+
+def large_stitch_values(batch, require_floor=True):
+    """the biggest scoring values under which the batch's largest pair still satisfies the domain condition; its largest term is the whole
+    budget T = (2^28 - 1) // (n1 + n2 + 2), which reaches 2^20 for pairs of up to 253 nodes together (require_floor asserts just that)"""
+    t = (STITCH_SCORE_BUDGET - 1) // (largest_pair(batch) + 2)
+    assert t >= 64, "batch too large for a 'large' parameter set"
+    if require_floor:
+        assert t >= LARGE_TERM_FLOOR, "the largest term %d of this batch's 'large' set is below 2^20" % t
+    return t // 4, t, (t // 8, t // 2, t - 1), (t // 16, t // 64, 1)
+
+
+def stitch_param_values(name, batch=None, require_floor=True):
+    if name == "large":
+        return large_stitch_values(batch, require_floor)
+    if name.startswith("random_"):
+        return draw_stitch_values(int(name[7:]))
+    return STITCH_SETS[name]
+
+
+def check_stitch_domain(batch, params):
+    """the domain condition of the sweep, asserted before anything runs: beyond it the reference's int32_t scores overflow (undefined)"""
+    ap = params.alignment_params
+    term = max([int(ap.match), int(ap.mismatch)] + [int(ap.gap_open[k]) + int(ap.gap_extend[k]) for k in range(3)])
+    assert all(ap.gap_open[k] <= ap.gap_open[k + 1] and ap.gap_extend[k] >= ap.gap_extend[k + 1] for k in range(2))
+    assert (largest_pair(batch) + 2) * term < STITCH_SCORE_BUDGET, "outside the reference's int32 domain: %d nodes x %d" % (largest_pair(batch), term)
+    return term
+
+
+def stitch_params(name, batch=None, require_floor=True):
+    """the named StitchParams ('large' is built for the batch); the domain condition is checked when a batch is given"""
+    p = _stitch_params_from(*stitch_param_values(name, batch, require_floor))
+    if batch is not None:
+        check_stitch_domain(batch, p)
+    return p
+
+
+_DEF_OPEN, _DEF_EXT = (1.25, 50.0, 5000.0), (2.5, 0.1, 0.0015)
+# name -> fields of ChainParams that differ from capi.default_chain_params()
+CHAIN_SETS = {
+    "default": {},
+    "fn0": dict(anchor_score_function=0),
+    "fn1": dict(anchor_score_function=1),
+    "fn3": dict(anchor_score_function=3),
+    "zero_open": dict(gap_open=(0.0, 0.0, 0.0)),
+    "flat_tail": dict(gap_extend=(2.5, 0.1, 0.0)),
+    "equal_pieces": dict(gap_open=(10.0, 10.0, 10.0), gap_extend=(0.5, 0.5, 0.5)),
+    "no_gap_cost": dict(gap_open=(0.0, 0.0, 0.0), gap_extend=(0.0, 0.0, 0.0)),
+    "heavy": dict(gap_open=tuple(x * 1000 for x in _DEF_OPEN), gap_extend=tuple(x * 1000 for x in _DEF_EXT)),
+    "light": dict(gap_open=tuple(x * 1e-4 for x in _DEF_OPEN), gap_extend=tuple(x * 1e-4 for x in _DEF_EXT)),
+    "count_power_0.25": dict(pair_count_power=0.25),
+    "count_power_1.5": dict(pair_count_power=1.5),
+    "length_1_flat": dict(length_intercept=1.0, length_decay_power=0.0),
+    "length_1_square": dict(length_intercept=1.0, length_decay_power=2.0),
+    "length_4000_flat": dict(length_intercept=4000.0, length_decay_power=0.0),
+    "length_4000_square": dict(length_intercept=4000.0, length_decay_power=2.0),
+}
+CHAIN_SCALES = (1.0, 0.05, 7.5)
+
+
+def chain_params(name, global_anchoring=True):
+    p = capi.default_chain_params(global_anchoring=global_anchoring)
+    for k, v in CHAIN_SETS[name].items():
+        if k in ("gap_open", "gap_extend"):
+            getattr(p, k)[:] = list(v)
+        else:
+            setattr(p, k, v)
+    assert all(p.gap_open[k] <= p.gap_open[k + 1] and p.gap_extend[k] >= p.gap_extend[k + 1] >= 0 for k in range(2)) and p.gap_open[0] >= 0
+    return p
+
+
+def draw_chain_params(seed, global_anchoring=True):
+    """a random valid ChainParams for the fuzz campaign: a named set's score function with gap pieces drawn like the stitch ones, scaled"""
+    rng = np.random.default_rng(8800 + seed)
+    p = capi.default_chain_params(global_anchoring=global_anchoring)
+    mag = float(rng.choice([1e-3, 1.0, 50.0]))
+    p.gap_open[:] = sorted(float(x) * mag for x in rng.choice(STITCH_DRAW_VALUES, 3))
+    p.gap_extend[:] = sorted((float(x) * mag * 0.01 for x in rng.choice(STITCH_DRAW_VALUES, 3)), reverse=True)
+    p.anchor_score_function = int(rng.integers(0, 4))
+    p.pair_count_power = float(rng.choice([0.25, 0.5, 1.0, 1.5]))
+    return p
+
+
+# the small seeded inputs of tests/golden/popoa_param_sweep.npz: name -> batch (rebuilt from synth, nothing but results is stored)
+def sweep_stitch_batches():
+    """(no empty graphs: the reference sends a pair with an empty side through Stitcher::subalign whatever NumPW is asked for, which is undefined under
+    the sets with a repeated extend; such a pair is a pure deletion under any scoring)"""
+    out = {}
+    out["dags"] = synth.random_dag_batch(120, seed=301, max_n=60, allow_empty=False)
+    out["dags"].only_deletion_alns[:] = 0
+    out["dags2"] = synth.random_dag_batch(60, seed=302, max_n=110, alphabet=2, allow_empty=False)
+    out["dags2"].only_deletion_alns[:] = 0
+    # chains with indels long enough to cross gap length 21 (the second crossover of near_crossovers)
+    sizes = [(1, 1), (3, 30), (30, 3), (40, 70), (70, 40), (64, 90), (100, 60), (17, 17), (16, 48), (48, 16), (33, 2), (120, 125), (90, 118)]
+    out["chains"] = synth.linear_batch(sizes, seed=303, divergence=0.08)
+    out["chains_far"] = synth.linear_batch(sizes, seed=304, divergence=0.5)
+    out["near_chains"] = synth.near_chain_batch([(20, 100), (100, 20), (64, 120), (90, 90), (5, 110), (120, 60), (40, 44)], seed=305, p_snp=0.08, p_del=0.06,
+                                                n_long=(0, 1), long_min=22, long_max=40)
+    return out
+
+
+def sweep_chain_cases():
+    """(case name, graph1, graph2, MatchSets) of tests/golden/chain_param_sweep.npz: budgeted subsets of the committed chain4_* match sets"""
+    from oracle import pyoracle as po
+    from tests.test_extraction import load_stitch_case
+    out = []
+    for m, (tag, budget, seed) in enumerate([("a", 1500, 11), ("b", 2500, 12), ("a", 2500, 13)]):
+        z = np.load(os.path.join(GOLDEN, "chain4_30k_merge%d.npz" % m))
+        _, graphs, _ = load_stitch_case("stitch4_30k_merge%d.npz" % m)
+        full = capi.MatchSets(**{k: z["%s.ms.%s" % (tag, k)] for k in capi.MatchSets._DT})
+        out.append(("merge%d" % m, graphs[0], graphs[1], po.budget_subset(full, budget, seed=seed)))
+    return out
+
+
+def alignment_values(params):
+    ap = params.alignment_params
+    return [int(ap.match), int(ap.mismatch)] + [int(x) for x in ap.gap_open] + [int(x) for x in ap.gap_extend]
+
+
+def subalign_defined(params):
+    """Stitcher::subalign derives its piece cutoffs by dividing by gap_extend[i-1] - gap_extend[i] (src/stitcher.cpp:39-43): with two equal
+    neighbouring extends the reference divides by zero, and the library answers CL_ERR_BAD_GAP_PARAMS; po_poa with a given NumPW is defined"""
+    ge = params.alignment_params.gap_extend
+    return ge[0] != ge[1] and ge[1] != ge[2]
+
+
+def pair_digests(res):
+    """a 64-bit digest of every alignment of a StitchResult (the goldens of the sweep store these instead of the pairs)"""
+    out = np.zeros(res.n_problems, np.uint64)
+    for k in range(res.n_problems):
+        out[k] = np.frombuffer(hashlib.sha256(np.ascontiguousarray(res.alignment(k), np.uint64).tobytes()).digest()[:8], np.uint64)[0]
+    return out
+
+
+def pack_sweep_result(res, prefix):
+    return {prefix + "aln_off": res.aln_off.astype(np.uint32), prefix + "digest": pair_digests(res), prefix + "score": res.score.astype(np.int64),
+            prefix + "route": res.route, prefix + "num_pw": res.num_pw}
+
+
+def sweep_result_diff(res, z, prefix, check_score, check_choice):
+    """None if a StitchResult is the stored one, else the first difference"""
+    if not np.array_equal(res.aln_off, z[prefix + "aln_off"]):
+        return "alignment lengths differ first at problem %d" % int(np.argmax(np.diff(res.aln_off.astype(np.int64)) != np.diff(z[prefix + "aln_off"].astype(np.int64))))
+    d = pair_digests(res)
+    if not np.array_equal(d, z[prefix + "digest"]):
+        return "alignment differs first at problem %d" % int(np.argmax(d != z[prefix + "digest"]))
+    if check_choice and not (np.array_equal(res.route, z[prefix + "route"]) and np.array_equal(res.num_pw, z[prefix + "num_pw"])):
+        return "route / num_pw differ"
+    if check_score:
+        m = z[prefix + "route"] == 0
+        if not np.array_equal(res.score[m], z[prefix + "score"][m]):
+            return "score differs at problem %d" % int(np.flatnonzero(m)[np.argmax(res.score[m] != z[prefix + "score"][m])])
+    return None

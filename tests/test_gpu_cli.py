@@ -84,6 +84,29 @@ def test_gpu_cli_from_a_config_file(tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("threads", [1, 3])
+def test_gpu_cli_away_from_the_default_scoring(tmp_path, threads):
+    """the one end-to-end run under non-default scoring (tests/golden/params_msa4_8k.yaml: stitch 3 / 4 / 2,9,30 / 5,2,1, anchor gaps 0,10,10 / 0.5,0.5,0, score function 1,
+    count power 0.75), where host routes, partitioning and calibration see it together with the kernels: the GFA and the -s subalignment text of the compiled
+    reference (tests/golden/make_golden.py msa_params), byte for byte, with one and with three worker contexts.  (On this input the reference's GFA under this
+    config is the GFA under the default scoring: the case shows that the library follows the reference there, not that the scoring moves the result.)"""
+    import gzip
+    case = [c for c in H.msa_cases() if c[0] == "msa4_8k"][0]
+    fa, nwk, budget, _ = msa_case(tmp_path, case)
+    text = open(os.path.join(H.GOLDEN, "params_msa4_8k.yaml")).read()
+    for key, old, new in (("fasta_name", '""', str(fa)), ("tree_name", '""', str(nwk)), ("max_num_match_pairs", "1250000", str(budget)),
+                          ("subalignments_filepath", '""', str(tmp_path / "sub.txt")), ("threads", "1", str(threads)), ("logging_level", "2", "1")):
+        assert text.count(" %s: %s\n" % (key, old)) == 1, key
+        text = text.replace(" %s: %s\n" % (key, old), " %s: %s\n" % (key, new))
+    (tmp_path / "run.yaml").write_text(text)
+    r = run(["-C", tmp_path / "run.yaml"], tmp_path)
+    want = gzip.open(os.path.join(H.GOLDEN, "params_msa4_8k.gfa.gz")).read()
+    assert r.stdout == want
+    assert (tmp_path / "sub.txt").read_bytes() == gzip.open(os.path.join(H.GOLDEN, "params_msa4_8k.sub.txt.gz")).read()
+    assert b"warning" not in r.stderr
+
+
+@pytest.mark.gpu
 def test_gpu_cli_force_gfa_output(tmp_path):
     """two sequences: the root GFA with --force-gfa-output (the reference's root -S file), the CIGAR without"""
     from tests.test_gpu_subalignments import json_text

@@ -185,6 +185,14 @@ def test_error_reporting(gpu_ctx):
     with pytest.raises(capi.ClError) as e:
         gpu_ctx.stitch_batch_align(synth.linear_batch([(5, 5)]), bad)
     assert e.value.code == -2
+    # every other way of breaking the order of the pieces (opens must not decrease, extends must not increase), under non-default values too
+    for go, ge in (([60, 800, 700], [30, 5, 1]), ([60, 800, 2500], [30, 31, 1]), ([60, 800, 2500], [30, 5, 6]), ([0, 0, 0], [0, 1, 0]), ([3, 2, 2], [1, 1, 1])):
+        bad = capi.default_stitch_params()
+        bad.alignment_params.gap_open[:] = go
+        bad.alignment_params.gap_extend[:] = ge
+        with pytest.raises(capi.ClError) as e:
+            gpu_ctx.stitch_batch_align(synth.linear_batch([(5, 5), (40, 50)]), bad)
+        assert e.value.code == -2, (go, ge)
     # a cyclic "subgraph"
     b1, b2 = synth._SideBuilder(), synth._SideBuilder()
     b1.add_graph(np.array([1, 2], np.uint8), [(0, 1), (1, 0)], [0], [1])
