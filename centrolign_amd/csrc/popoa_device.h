@@ -1,6 +1,6 @@
 // popoa_device.h — device-side data layout of a packed stitch batch (shared by host packer and kernels).
 //
-// Everything the kernels read is in TOPOLOGICAL-RANK space: the host packer (cl_api.cpp) orders every
+// Everything the kernels read is in TOPOLOGICAL-RANK space: the host packer (cl_stitch_plan_api.cpp) orders every
 // subgraph once (Kahn, as include/centrolign/topological_order.hpp:12-60 of the reference) and rewrites
 // labels / predecessor lists / sinks in rank order, so that an anti-diagonal  a + b = d  of the
 // (n1+1) x (n2+1) matrix only depends on earlier anti-diagonals.  Index 0 on each axis is the reference's

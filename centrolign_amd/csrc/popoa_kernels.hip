@@ -1477,7 +1477,7 @@ hipError_t cl_launch_popoa_narrow(int threads, uint32_t n_blocks, uint32_t lds_b
     return hipGetLastError();
 }
 
-// host-callable launcher (C++ linkage, used by cl_api.cpp only)
+// host-callable launcher (C++ linkage, used by cl_stitch_exec_api.cpp only)
 // ring_bytes > 0: the LDS-ring variant (every problem of the launch has its ring depth in ClProbDesc::pad and fits ring_bytes)
 hipError_t cl_launch_popoa_lane(int W, uint32_t n_blocks, uint32_t lds_bytes, const ClDeviceBatch& B, const uint32_t* plist, const ClScoreParams& P, uint32_t* lane_sync, hipStream_t stream) {
     if (n_blocks == 0) return hipSuccess;

@@ -38,7 +38,7 @@
 //     the traceback.
 // Model of the data movement, checked against the plain pull-form DP: scripts/dev/nearchain_model.py.
 //
-// Records (host: cl_api.cpp), uint32 each, at ClDeviceBatch::aux + ClProbDesc::aux_base: sync | rowrec[nR] | rowdist[nR] | colrec[nC] | coldist[nC]
+// Records (host: choose_lane, cl_stitch_plan_api.cpp), uint32 each, at ClDeviceBatch::aux + ClProbDesc::aux_base: sync | rowrec[nR] | rowdist[nR] | colrec[nC] | coldist[nC]
 //   sync  : a WIDE pair's first progress word in the plan's lane_sync array (progress[groups] | done[groups]); 0 otherwise
 //   rowrec: bits 0-3 predecessor distances (bit d - 1) | bit 4 source | bits 8-14 label
 //   colrec: bits 0-2 near predecessor distances (1 .. 3 columns back) | bit 4 source | bits 5-6 number of saved-column predecessors | bits 8-14 label | bit 15 this column is saved,

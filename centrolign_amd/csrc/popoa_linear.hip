@@ -565,7 +565,7 @@ __global__ void __launch_bounds__(64 * W) popoa_linear_kernel(ClDeviceBatch B, c
 // steps.  Here a wave takes FOUR of them: lanes 16 g .. 16 g + 15 are pair g's rows, the systolic moves are the ROW forms of the same DPP controls
 // (row_shr:1 / row_shl:1 act inside rows of 16 lanes: lane 0 of a row keeps the fill), the column feed is a chunk of 16 columns per segment.  Same cell, same
 // codes at the same addresses as linear_body<NPW, 1, 1, SWAP> (a pair's code buffer is indexed by ITS step and ITS lane), so linear_traceback walks them
-// unchanged, one pair after the other.  The quad's pairs have the same NumPW (host: cl_api.cpp sorts them by NumPW and length); 0xFFFFFFFF = no pair.
+// unchanged, one pair after the other.  The quad's pairs have the same NumPW (host: form_quad_duo_groups, cl_stitch_plan_api.cpp, sorts them by NumPW and length); 0xFFFFFFFF = no pair.
 // SEG = lanes of a segment = rows a pair may have: 16 (four pairs per wave, the ROW forms of the DPP moves) or 32 (two pairs per wave — round 5, second half: the
 // 17 000 pairs of 17-32 rows of a 10 x 1 Mbp step cost a wave 110 steps each alone, 80 steps per two here; the wave forms of the moves, and the one lane that would
 // take its neighbour segment's value — lane 32 — takes the fill by a select).  rotate_down needs no such care: what enters a segment's last lane from the next

@@ -450,7 +450,7 @@ def test_far_forks_in_both_graphs_take_the_level_order(gpu_ctx, monkeypatch):
     """(round 5) Long bubbles whose two branches are BOTH long — two diverged copies of a repeat unit — in both graphs of a pair.  In the reference's topological order
     (branches one after the other) the second branch and the closing node read a whole branch back in the row graph AND the column graph: such a pair was left to the
     anti-diagonal sweep in rounds 1-4 (missing #3).  The packer now ranks a graph by LEVEL (longest path from a source) when that shortens its reads
-    (choose_rank_order, cl_api.cpp): the branches interleave, the pair meets the conditions of the register kernel / the strips.  Nothing in the result may depend on
+    (choose_rank_order, cl_stitch_plan_api.cpp): the branches interleave, the pair meets the conditions of the register kernel / the strips.  Nothing in the result may depend on
     the order: against the oracle, and the reference's order (CL_RANK_ORDER=lifo) against the level order (=level) and the choice (default), every NumPW"""
     monkeypatch.setenv("CL_LANE_MIN_SWEEP", "0")
     sizes = [(3000, 3200), (1500, 1400), (700, 650), (300, 2500), (2600, 420), (150, 160)]

@@ -1,4 +1,4 @@
-"""CPU suite: the topological order the device ranks a subgraph's nodes by (cl_stitch_rank_order = choose_rank_order of the packer, centrolign_amd/csrc/cl_api.cpp; round 5).
+"""CPU suite: the topological order the device ranks a subgraph's nodes by (cl_stitch_rank_order = choose_rank_order of the packer, centrolign_amd/csrc/cl_stitch_plan_api.cpp; round 5).
 The result of a subproblem does not depend on the order (that is what the -m gpu parity tests hold: reference order = level order = the choice); what is checked here is
 the host logic: every order returned is a topological order; chains and graphs whose bubbles have one short branch keep the reference's order
 (topological_order.hpp:12-60, restated in oracle/); a bubble with two long branches is interleaved by the level order, which the choice then takes; the counts
