@@ -429,6 +429,52 @@ def induced_pairwise_cigars(graph, pairs, ctx):
     return [text[int(off[k]):int(off[k + 1])] for k in range(n)]
 
 
+PAIR_STATS_FIELDS = ("eq", "x", "ins", "del", "eq_runs", "x_runs", "ins_runs", "del_runs")   # cl_pair_stats, in the struct's order
+
+
+def induced_pairwise_stat(graph, path1, path2):
+    """cl_induced_pairwise_stat (host only): what parsing induced_pairwise_cigar(graph, path1, path2) gives, as a dict over PAIR_STATS_FIELDS —
+    bases in '=', 'X', 'I', 'D' runs and the number of runs of each letter"""
+    lib = load_library()
+    g, out = graph.as_c(), np.zeros(8, np.uint64)
+    lib.cl_induced_pairwise_stat.restype = C.c_int
+    lib.cl_induced_pairwise_stat.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64, C.c_void_p]
+    rc = lib.cl_induced_pairwise_stat(C.byref(g), int(path1), int(path2), out.ctypes.data)
+    if rc != 0:
+        raise ClError(rc, "cl_induced_pairwise_stat")
+    return dict(zip(PAIR_STATS_FIELDS, (int(v) for v in out)))
+
+
+def induced_pairwise_stats(graph, pairs, ctx):
+    """cl_induced_pairwise_stats: induced_pairwise_stat of every (path1, path2) row of `pairs` in one device pass on Context ctx; a uint64 array
+    [len(pairs), 8] with PAIR_STATS_FIELDS as columns.  Raises ClError with the host function's code for the first failing pair."""
+    lib = load_library()
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+    n = len(pairs)
+    g, out = graph.as_c(), np.zeros((n, 8), np.uint64)
+    lib.cl_induced_pairwise_stats.restype = C.c_int
+    lib.cl_induced_pairwise_stats.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.c_void_p, C.c_uint64, C.c_void_p]
+    ctx._check(lib.cl_induced_pairwise_stats(ctx.handle, C.byref(g), pairs.ctypes.data, n, out.ctypes.data))
+    return out
+
+
+def alignment_distances(stats, n):
+    """cl_alignment_distances (host only): the [n, n] float64 matrix d = 1 - 2 eq / (2 eq + 2 x + ins + del) of the n * (n - 1) / 2 rows of `stats`
+    (induced_pairwise_stats of the pairs (a, b), a < b, a outer)"""
+    lib = load_library()
+    st = np.ascontiguousarray(np.asarray(stats, np.uint64).reshape(-1, 8))
+    n = int(n)
+    if len(st) != max(n * (n - 1) // 2, 0):
+        raise ValueError("stats must have %d rows for n = %d, got %d" % (n * (n - 1) // 2, n, len(st)))
+    out = np.zeros((max(n, 1), max(n, 1)), np.float64)
+    lib.cl_alignment_distances.restype = C.c_int
+    lib.cl_alignment_distances.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    rc = lib.cl_alignment_distances(st.ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise ClError(rc, "cl_alignment_distances")
+    return out
+
+
 def induced_cyclic_maf(graph, path1, path2, name1, name2):
     """output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), …) (src/alignment.cpp:569-904): the CLI's -A output after
     cyclisation, for two paths of a graph that may have cycles; name1 / name2 are the paths' names.  bytes"""
@@ -755,12 +801,32 @@ class PolishParams(C.Structure):
 
 
 class MsaParams(C.Structure):
-    """cl_msa_params"""
+    """cl_msa_params up to force_gfa_output, the layout every caller written before pair_stats_path knows; MsaParamsFull below is the whole
+    struct.  The library reads and writes the whole struct whatever it is handed, so an instance of this class is made with room for the
+    fields that follow (__new__): code that fills a plain MsaParams with cl_msa_params_default and passes it on keeps working, with the new
+    fields as the default leaves them.
+    CAUTION for whoever appends the next field: add it to MsaParamsFull, never here — tests/test_subalignments.py pins this class's last three
+    fields, which is the only reason there are two classes; once that test may change, fold them into one.  __new__ does not run for an
+    MsaParams embedded in another Structure or an array: embed MsaParamsFull there."""
+    def __new__(cls, *args, **kw):
+        obj = super().__new__(cls, *args, **kw)
+        if C.sizeof(cls) < MSA_PARAMS_BYTES:
+            C.resize(obj, MSA_PARAMS_BYTES)
+        return obj
+
     _fields_ = [("merge", MergeParams), ("skip_calibration", C.c_int), ("n_workers", C.c_int), ("devices", C.POINTER(C.c_int)), ("n_devices", C.c_int),
                 ("subproblems_prefix", C.c_char_p), ("restart", C.c_int),
                 ("induced_pairwise_prefix", C.c_char_p), ("cyclize", C.c_int), ("max_tandem_duplication_search_rounds", C.c_uint64),
                 ("bonds", BondParams), ("polish", PolishParams),
                 ("subalignments_path", C.c_char_p), ("bonds_prefix", C.c_char_p), ("force_gfa_output", C.c_int)]
+
+
+class MsaParamsFull(MsaParams):
+    """cl_msa_params: MsaParams and the fields appended after it (a ctypes subclass lays its fields out behind the base's, as C does)"""
+    _fields_ = [("pair_stats_path", C.c_char_p)]
+
+
+MSA_PARAMS_BYTES = C.sizeof(MsaParamsFull)
 
 
 class MsaStats(C.Structure):
@@ -1169,7 +1235,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 15    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 16    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1384,6 +1450,7 @@ EXPORTED_SYMBOLS = [
     "cl_config_default", "cl_config_free", "cl_config_set", "cl_config_get", "cl_config_parse", "cl_config_generate", "cl_config_validate",
     "cl_config_msa_params",
     "cl_kmer_distances_compute", "cl_kmer_distances_free", "cl_neighbor_joining_newick", "cl_infer_guide_tree",
+    "cl_induced_pairwise_stat", "cl_induced_pairwise_stats", "cl_alignment_distances", "cl_refine_guide_tree",
 ]
 
 
@@ -1435,7 +1502,8 @@ class Config:
         self._check(self.lib.cl_config_validate(self.handle))
 
     def msa_params(self):
-        """the cl_msa_params this config runs with (string fields point into this object: keep it alive while they are used)"""
+        """the cl_msa_params this config runs with (string fields point into this object: keep it alive while they are used).  No parameter
+        sets a field behind force_gfa_output, so this is the MsaParams view; MsaParamsFull.from_buffer(mp) reaches the rest"""
         mp = MsaParams()
         self._check(self.lib.cl_config_msa_params(self.handle, C.byref(mp)))
         return mp
@@ -1962,13 +2030,46 @@ class Context:
 
     def msa(self, fasta_text, newick=None, max_num_match_pairs=1250000, max_count=3000, skip_calibration=False, subproblems_prefix=None,
             restart=False, induced_pairwise_prefix=None, workers=1, cyclize=False, min_cyclizing_length=None, devices=None, chaining_algorithm=None,
-            subalignments_path=None, bonds_prefix=None, force_gfa_output=False):
+            subalignments_path=None, bonds_prefix=None, force_gfa_output=False, pair_stats_path=None):
         """the whole CLI flow in the library (cl_msa): FASTA text (+ Newick text) -> explicit CIGAR (two sequences) or GFA; returns
         (text bytes, stats dict).  cyclize = the CLI's -c, min_cyclizing_length its -y; devices = device ordinals the worker contexts are
         spread over (worker w on devices[w % len(devices)]; one process, several GPUs); subalignments_path = -s, bonds_prefix = --bond-prefix,
-        force_gfa_output = --force-gfa-output"""
+        force_gfa_output = --force-gfa-output, pair_stats_path = --pair-stats"""
         raw = fasta_text.encode() if isinstance(fasta_text, str) else bytes(fasta_text)
-        mp = MsaParams()
+        mp, _keep = self._msa_params(max_num_match_pairs, max_count, skip_calibration, subproblems_prefix, restart, induced_pairwise_prefix, workers, cyclize,
+                                     min_cyclizing_length, devices, chaining_algorithm, subalignments_path, bonds_prefix, force_gfa_output, pair_stats_path)
+        p, n, st = C.c_void_p(), C.c_uint64(0), MsaStats()
+        self._check(self.lib.cl_msa(self.handle, raw, len(raw), None if not newick else newick.encode(), C.byref(mp), C.byref(p), C.byref(n), C.byref(st)))
+        try:
+            return C.string_at(p, int(n.value)), {k: getattr(st, k) for k, _ in MsaStats._fields_}
+        finally:
+            _libc_free(p)
+
+    def refine_guide_tree(self, fasta_text, newick=None, max_rounds=1, max_num_match_pairs=1250000, max_count=3000, skip_calibration=False, workers=1,
+                          devices=None, chaining_algorithm=None):
+        """cl_refine_guide_tree: up to max_rounds rounds of align (cl_msa under the current tree, these scoring / budget / worker settings, no side
+        output) -> induced_pairwise_stats -> alignment_distances in FASTA order -> neighbor_joining_newick; returns (Newick text, or None when
+        no round ran from the in-order tree; rounds run; converged)"""
+        raw = fasta_text.encode() if isinstance(fasta_text, str) else bytes(fasta_text)
+        mp, _keep = self._msa_params(max_num_match_pairs, max_count, skip_calibration, None, False, None, workers, False, None, devices, chaining_algorithm,
+                                     None, None, False, None)
+        self.lib.cl_refine_guide_tree.restype = C.c_int
+        self.lib.cl_refine_guide_tree.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(MsaParams), C.c_int, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        p, n, rounds, conv = C.c_void_p(), C.c_uint64(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.cl_refine_guide_tree(self.handle, raw, len(raw), None if newick is None else newick.encode(), C.byref(mp), int(max_rounds),
+                                                  C.byref(p), C.byref(n), C.byref(rounds), C.byref(conv)))
+        if not p.value:
+            return None, int(rounds.value), bool(conv.value)
+        try:
+            return C.string_at(p, int(n.value)).decode(), int(rounds.value), bool(conv.value)
+        finally:
+            _libc_free(p)
+
+    def _msa_params(self, max_num_match_pairs, max_count, skip_calibration, subproblems_prefix, restart, induced_pairwise_prefix, workers, cyclize,
+                    min_cyclizing_length, devices, chaining_algorithm, subalignments_path, bonds_prefix, force_gfa_output, pair_stats_path):
+        """cl_msa_params_default with msa()'s keywords applied; the second item keeps the device list alive"""
+        mp = MsaParamsFull()
         self.lib.cl_msa_params_default(C.byref(mp))
         mp.merge.match.max_count = int(max_count)
         mp.merge.align.anchor.max_num_match_pairs = int(max_num_match_pairs)
@@ -1987,14 +2088,10 @@ class Context:
         mp.subalignments_path = subalignments_path.encode() if subalignments_path else None   # -s
         mp.bonds_prefix = bonds_prefix.encode() if bonds_prefix else None                     # --bond-prefix
         mp.force_gfa_output = int(force_gfa_output)                                           # --force-gfa-output
+        mp.pair_stats_path = pair_stats_path.encode() if pair_stats_path else None            # --pair-stats
         if min_cyclizing_length is not None:
             mp.bonds.min_length = float(min_cyclizing_length)                                 # -y
-        p, n, st = C.c_void_p(), C.c_uint64(0), MsaStats()
-        self._check(self.lib.cl_msa(self.handle, raw, len(raw), None if not newick else newick.encode(), C.byref(mp), C.byref(p), C.byref(n), C.byref(st)))
-        try:
-            return C.string_at(p, int(n.value)), {k: getattr(st, k) for k, _ in MsaStats._fields_}
-        finally:
-            _libc_free(p)
+        return mp, dev_arr
 
     def plan(self, batch, params=None, force_num_pw=None):
         params = params or default_stitch_params()

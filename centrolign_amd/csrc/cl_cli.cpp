@@ -6,6 +6,8 @@
 //   - -t N runs N worker contexts; --devices LIST places them (cl_msa_params.devices);
 //   - --infer-tree infers the guide tree from k-mer distances (cl_infer_guide_tree) where the reference needs one from outside; --tree-out
 //     writes it;
+//   - --refine-tree N rebuilds the guide tree from the distances of an alignment made under it (cl_refine_guide_tree), up to N times, before the
+//     alignment proper; --pair-stats and --dist-out write the pairwise statistics and distances the final alignment implies;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -14,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <string>
 #include <vector>
 
@@ -88,6 +91,62 @@ bool parse_devices(const char* text, std::vector<int>& out) {
     return !out.empty();
 }
 
+// --dist-out: the rows of a --pair-stats file (pairs (p, q), p < q, of the root graph's paths, named as -A names its files) -> cl_alignment_distances
+// -> the matrix in FASTA order: a line with n, then per sequence its name and n values
+bool write_distances(const std::string& stats_file, const std::vector<std::string>& names, const std::string& dist_file, std::string& err) {
+    const uint64_t n = names.size();
+    std::ifstream in(stats_file, std::ios::binary);
+    std::string line;
+    std::vector<cl_pair_stats> stats;
+    std::vector<std::string> path_names;
+    if (!in || !std::getline(in, line)) { err = "could not read the pair statistics from " + stats_file; return false; }
+    while (std::getline(in, line)) {
+        std::vector<std::string> f;
+        for (size_t at = 0;;) {
+            const size_t e = line.find('\t', at);
+            f.push_back(line.substr(at, e == std::string::npos ? e : e - at));
+            if (e == std::string::npos) break;
+            at = e + 1;
+        }
+        if (f.size() != 11) { err = "unexpected line in " + stats_file + ": " + line; return false; }
+        if (stats.empty()) path_names.push_back(f[0]);
+        if (stats.size() + 1 < n) path_names.push_back(f[1]);
+        cl_pair_stats s;
+        uint64_t* v[8] = {&s.eq, &s.x, &s.ins, &s.del, &s.eq_runs, &s.x_runs, &s.ins_runs, &s.del_runs};
+        for (int i = 0; i < 8; ++i) *v[i] = strtoull(f[2 + i].c_str(), nullptr, 10);
+        stats.push_back(s);
+    }
+    if (stats.size() != n * (n - 1) / 2 || path_names.size() != n) { err = stats_file + " does not hold every pair of sequences"; return false; }
+    std::vector<uint64_t> seq_of(n, n);   // path -> FASTA index, by the name -A gives the sequence
+    for (uint64_t q = 0; q < n; ++q) {
+        std::string nm = names[q];
+        for (char& c : nm) if (c == '/') c = '_';
+        uint64_t p = 0;
+        while (p < n && path_names[p] != nm) ++p;
+        if (p == n || seq_of[p] != n) { err = "sequence " + names[q] + " has no rows of its own in " + stats_file + " (names that differ only in '/' and '_' share one)"; return false; }
+        seq_of[p] = q;
+    }
+    std::vector<double> by_path(n * n), by_seq(n * n);
+    if (cl_alignment_distances(stats.data(), n, by_path.data())) { err = "could not compute the alignment distances"; return false; }
+    for (uint64_t p = 0; p < n; ++p)
+        for (uint64_t q = 0; q < n; ++q) by_seq[seq_of[p] * n + seq_of[q]] = by_path[p * n + q];
+    std::string text = std::to_string(n) + "\n";
+    for (uint64_t a = 0; a < n; ++a) {
+        text += names[a];
+        for (uint64_t b = 0; b < n; ++b) {
+            char num[40];
+            snprintf(num, sizeof(num), "\t%.9g", by_seq[a * n + b]);
+            text += num;
+        }
+        text += '\n';
+    }
+    std::ofstream out(dist_file, std::ios::binary);
+    if (out) out.write(text.data(), (std::streamsize)text.size());
+    out.close();
+    if (!out) { err = "could not write the distance matrix to " + dist_file; return false; }
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -118,11 +177,15 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --bond-prefix PREFIX        With -c, write the alignment of every tandem duplication found to files starting with PREFIX\n");
     fprintf(o, " --devices LIST              Comma-separated GPU ordinals the worker contexts are spread over [the first GPU]\n");
     fprintf(o, " --infer-tree                Infer the guide tree from k-mer distances (k = 21, neighbor joining) instead of taking one\n");
-    fprintf(o, " --tree-out FILE             With --infer-tree, write the inferred Newick tree to FILE\n");
+    fprintf(o, " --refine-tree INT           Rebuild the guide tree from the distances of an alignment made under it, up to INT times, then align\n");
+    fprintf(o, " --tree-out FILE             With --infer-tree or --refine-tree, write the Newick tree the alignment used to FILE\n");
+    fprintf(o, " --pair-stats FILE           Write matches, mismatches, gap bases, runs and distance of every pair of sequences to FILE (which must not exist yet)\n");
+    fprintf(o, " --dist-out FILE             Write the matrix of pairwise alignment distances, in FASTA order, to FILE\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
-    fprintf(o, "-t sets worker contexts; --devices, --infer-tree and --tree-out are added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats and --dist-out are added; -v gates this tool's own\n");
+    fprintf(o, "progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -144,11 +207,12 @@ int run(int argc, char** argv) {
     cl_config* cfg = own.cfg;
 
     std::string config_name;
-    std::string tree_out;
+    std::string tree_out, pair_stats, dist_out, refine_arg;
     bool force_gfa_output = false, generate_config = false, infer_tree = false;
     std::vector<int> devices;
 
-    enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006 };
+    enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
+           OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -173,6 +237,9 @@ int run(int argc, char** argv) {
         {"devices", required_argument, nullptr, OPT_DEVICES},
         {"infer-tree", no_argument, nullptr, OPT_INFER_TREE},
         {"tree-out", required_argument, nullptr, OPT_TREE_OUT},
+        {"pair-stats", required_argument, nullptr, OPT_PAIR_STATS},
+        {"dist-out", required_argument, nullptr, OPT_DIST_OUT},
+        {"refine-tree", required_argument, nullptr, OPT_REFINE_TREE},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -207,6 +274,9 @@ int run(int argc, char** argv) {
             break;
         case OPT_INFER_TREE: infer_tree = true; break;
         case OPT_TREE_OUT: tree_out = optarg; break;
+        case OPT_PAIR_STATS: pair_stats = optarg; break;
+        case OPT_DIST_OUT: dist_out = optarg; break;
+        case OPT_REFINE_TREE: refine_arg = optarg; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -246,7 +316,20 @@ int run(int argc, char** argv) {
 
     // the tree options of this project, checked before anything is read or opened
     if (infer_tree && !config_value(cfg, "tree_name").empty()) return fail("--infer-tree cannot be combined with a guide tree (-T or tree_name)");
-    if (!tree_out.empty() && !infer_tree) return fail("--tree-out needs --infer-tree");
+    if (!tree_out.empty() && !infer_tree && refine_arg.empty()) return fail("--tree-out needs --infer-tree");
+    int refine_rounds = 0;
+    if (!refine_arg.empty()) {
+        char* end = nullptr;
+        errno = 0;
+        const long v = strtol(refine_arg.c_str(), &end, 10);
+        if (*end || errno || v < 1 || v > 1000000) return fail("--refine-tree expects a whole number of rounds, at least 1, got '" + refine_arg + "'");
+        refine_rounds = (int)v;
+        if (config_value(cfg, "restart") == "true") return fail("--refine-tree cannot be combined with a restart (-R)");
+    }
+    if (!pair_stats.empty() && std::ifstream(pair_stats).good()) return fail("Pair statistics file already exists: " + pair_stats);
+    // --dist-out alone passes the rows through a file of its own next to FILE, which must not be anybody else's
+    const std::string dist_tmp = !dist_out.empty() && pair_stats.empty() ? dist_out + ".pair-stats.tmp" : std::string();
+    if (!dist_tmp.empty() && std::ifstream(dist_tmp).good()) return fail("--dist-out would overwrite " + dist_tmp + ": remove it or give --pair-stats");
 
     if (cl_config_validate(cfg)) {
         fprintf(stderr, "error: %s\n", lib_error().c_str());
@@ -271,16 +354,27 @@ int run(int argc, char** argv) {
     cl_fasta fa;
     if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) return fail(lib_error());
     const uint64_t n_sequences = fa.n_sequences;
+    const std::vector<std::string> sequence_names(fa.names, fa.names + fa.n_sequences);
     cl_fasta_free(&fa);
     if (n_sequences < 2)
         return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains " + std::to_string(n_sequences) +
                     " sequence(s), cannot form an alignment");
-    if (tree_name.empty() && !infer_tree && n_sequences > 2)
+    if (!dist_out.empty()) {   // the rows name sequences as -A names its files: two names that differ only in '/' and '_' could not be told apart
+        std::vector<std::string> flat = sequence_names;
+        for (std::string& nm : flat) for (char& c : nm) if (c == '/') c = '_';
+        for (size_t a = 0; a < flat.size(); ++a)
+            for (size_t b = a + 1; b < flat.size(); ++b)
+                if (flat[a] == flat[b]) return fail("--dist-out cannot tell sequences " + sequence_names[a] + " and " + sequence_names[b] + " apart");
+    }
+    if (tree_name.empty() && !infer_tree && refine_rounds == 0 && n_sequences > 2)
         fprintf(stderr, "warning: it is highly recommended to provide a guide tree (-T) when aligning > 2 sequences\n");
 
     cl_msa_params mp;
     if (cl_config_msa_params(cfg, &mp)) return fail(lib_error());
     mp.force_gfa_output = force_gfa_output;
+    // --dist-out is computed from the rows of the --pair-stats file: without --pair-stats the run writes them next to FILE and the file is removed
+    const std::string stats_file = !pair_stats.empty() ? pair_stats : dist_tmp;
+    if (!stats_file.empty()) mp.pair_stats_path = stats_file.c_str();
     if (!devices.empty()) {
         mp.devices = devices.data();
         mp.n_devices = (int)devices.size();
@@ -307,12 +401,39 @@ int run(int argc, char** argv) {
         snprintf(line, sizeof(line), "Inferred the guide tree in %.3f s.", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
         log_line(LOG_VERBOSE, line);
         log_line(LOG_DEBUG, "guide tree: " + newick);
-        if (!tree_out.empty()) {
-            FILE* f = fopen(tree_out.c_str(), "wb");
-            const std::string text = newick + "\n";
-            const bool written = f && fwrite(text.data(), 1, text.size(), f) == text.size();
-            if ((f && fclose(f) != 0) || !written) return fail("could not write the guide tree to " + tree_out);
+    }
+    bool have_tree = !tree_name.empty() || infer_tree;   // false: cl_msa gets NULL, the sequences in FASTA order
+    if (refine_rounds > 0) {   // the refined tree goes to cl_msa exactly as the text of a -T file would
+        log_line(LOG_BASIC, "Refining the guide tree from alignment distances.");
+        const auto t0 = std::chrono::steady_clock::now();
+        int done = 0;
+        // One round per call, so that each round's tree can be logged at -v 4: the same rounds, trees and convergence as one call with max_rounds = N
+        // (a round depends on the tree text alone), at the price of parsing the FASTA once per round
+        for (int r = 0; r < refine_rounds; ++r) {
+            char* tree = nullptr;
+            uint64_t tree_len = 0;
+            int rounds_run = 0, converged = 0;
+            if (cl_refine_guide_tree(own.ctx, fasta_text.data(), fasta_text.size(), have_tree ? newick.c_str() : nullptr, &mp, 1, &tree, &tree_len, &rounds_run,
+                                     &converged)) {
+                const char* e = cl_last_error(own.ctx);
+                return fail(e && *e ? e : lib_error());
+            }
+            if (tree) { newick.assign(tree, tree_len); have_tree = true; }
+            free(tree);
+            if (rounds_run == 0) break;   // fewer than three sequences: nothing to refine
+            ++done;
+            log_line(LOG_DEBUG, "guide tree after round " + std::to_string(done) + ": " + newick);
+            if (converged) { log_line(LOG_VERBOSE, "The guide tree no longer changes."); break; }
         }
+        char line[128];
+        snprintf(line, sizeof(line), "Refined the guide tree in %d round(s), %.3f s.", done, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        log_line(LOG_VERBOSE, line);
+    }
+    if (!tree_out.empty()) {
+        FILE* f = fopen(tree_out.c_str(), "wb");
+        const std::string text = (have_tree ? newick : std::string()) + "\n";
+        const bool written = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+        if ((f && fclose(f) != 0) || !written) return fail("could not write the guide tree to " + tree_out);
     }
 
     log_line(LOG_BASIC, "Aligning " + std::to_string(n_sequences) + " sequences.");
@@ -320,13 +441,19 @@ int run(int argc, char** argv) {
     uint64_t len = 0;
     cl_msa_stats st;
     memset(&st, 0, sizeof(st));
-    if (cl_msa(own.ctx, fasta_text.data(), fasta_text.size(), tree_name.empty() && !infer_tree ? nullptr : newick.c_str(), &mp, &text, &len, &st)) {
+    if (cl_msa(own.ctx, fasta_text.data(), fasta_text.size(), have_tree ? newick.c_str() : nullptr, &mp, &text, &len, &st)) {
         const char* e = cl_last_error(own.ctx);
         return fail(e && *e ? e : lib_error());
     }
     const bool written = fwrite(text, 1, len, stdout) == len && fflush(stdout) == 0;
     free(text);
     if (!written) return fail("could not write the alignment to standard output");
+    if (!dist_out.empty()) {
+        std::string err;
+        const bool ok = write_distances(stats_file, sequence_names, dist_out, err);
+        if (pair_stats.empty()) remove(stats_file.c_str());
+        if (!ok) return fail(err);
+    }
 
     char line[512];
     snprintf(line, sizeof(line), "%llu merges, score scale %.6g: calibration %.2f s, matches %.2f s, alignment %.2f s, fusion %.2f s",

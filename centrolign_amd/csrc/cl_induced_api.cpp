@@ -1,6 +1,8 @@
 // cl_induced_api.cpp — the -A output of the CLI (src/core.cpp:523-591):
 //   cl_induced_pairwise_cigars  the CIGARs of many pairs of paths of an acyclic graph in one device pass (kernels: induced_kernels.hip); the
 //                               host restatement cl_induced_pairwise_cigar (cl_io_api.cpp) is what it is checked against
+//   cl_induced_pairwise_stats   the same alignments as counters (bases and runs per op) in one device pass of their own kernel, no text; it shares
+//                               the position tables and the chunking with the call above (induced_batch); host restatement: cl_induced_pairwise_stat
 //   cl_induced_cyclic_maf       output_maf(induced_cyclic_pairwise_alignment(...)) (src/alignment.cpp:229-904), the output after cyclisation.
 //                               Host code: its core is a Hunt-Szymanski LCS, a dependent chain of binary searches over a threshold row
 //                               (DESIGN.md §9); the caller runs pairs in parallel, as the reference does (core.cpp:554-591).
@@ -24,7 +26,7 @@ char* c_string(const std::string& s, uint64_t* len_out) {
 }
 
 constexpr uint64_t kGap = ~(uint64_t)0;
-// device working memory of one chunk of cl_induced_pairwise_cigars: the position tables of the chunk's first paths (4 bytes per node each);
+// device working memory of one chunk of cl_induced_pairwise_cigars / _stats: the position tables of the chunk's first paths (4 bytes per node each);
 // the text of a write pass is bounded the same way (a single pair's CIGAR may exceed it alone).  A chunk also holds at most kChunkPairs pairs.
 constexpr uint64_t kChunkTableBytes = 256ull << 20, kChunkTextBytes = 256ull << 20, kChunkPairs = 2048;
 
@@ -364,6 +366,101 @@ void maf_row(std::string& out, const std::string& name, uint64_t start, uint64_t
     out += '\n';
 }
 
+// ---------------------------------------------- what the device passes over pairs of paths share -----------------------------------------
+// One chunk of a batch, ready for a pass of induced_kernels.hip: the jobs (text_off / text_cap zero), the pair each job answers, and the device
+// arrays the kernels read (the graph's paths and labels, the chunk's position tables)
+struct InducedChunk {
+    std::vector<ClInducedJob> jobs;
+    std::vector<uint64_t> job_pair;
+    const uint32_t* d_nodes;
+    uint64_t n_steps;
+    const uint8_t* d_label;
+    const uint32_t* d_tables;
+};
+
+// The frame of cl_induced_pairwise_cigars and cl_induced_pairwise_stats: the checks the host makes (cl_induced_pairwise_cigar's order), the
+// graph on the device, the pairs ordered by first path and cut into chunks, each chunk's position tables (scatter + check), then pass(chunk)
+// for the entry point's own kernels and copies, and at the end the code of the first failing pair.
+template <class Pass>
+int induced_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, Pass&& pass) {
+    // what the host decides (cl_induced_pairwise_cigar's order): a path index out of range, then a path-1 node id out of range; a repeated path-1
+    // node is found on the device; then a path-2 node id out of range
+    std::vector<int8_t> bad_ids(g->n_paths, -1);
+    auto ids_bad = [&](uint64_t p) {
+        if (bad_ids[p] < 0) {
+            bad_ids[p] = 0;
+            for (uint64_t i = g->path_off[p]; i < g->path_off[p + 1]; ++i) if (g->path_nodes[i] >= g->n_nodes) { bad_ids[p] = 1; break; }
+            if (g->path_off[p + 1] - g->path_off[p] >= 0xFFFFFFFFull) bad_ids[p] = 1;   // positions are 32-bit words in the table
+        }
+        return bad_ids[p] == 1;
+    };
+    std::vector<int> pre(n_pairs, CL_OK);
+    std::vector<uint64_t> todo;   // pairs whose path 1 gets a position table, ordered by path 1
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        const uint64_t a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a >= g->n_paths || b >= g->n_paths) { pre[k] = CL_ERR_INVALID_ARGUMENT; continue; }
+        if (ids_bad(a)) { pre[k] = CL_ERR_CYCLIC_GRAPH; continue; }
+        todo.push_back(k);
+    }
+    std::stable_sort(todo.begin(), todo.end(), [&](uint64_t x, uint64_t y) { return pairs[2 * x] < pairs[2 * y]; });
+    std::vector<uint8_t> repeated(g->n_paths, 0);
+    const uint64_t n_steps = g->path_off[g->n_paths];
+    DevBuf<uint32_t> d_nodes;
+    DevBuf<uint8_t> d_label;
+    int rc;
+    if (!todo.empty()) {
+        if ((rc = d_nodes.alloc(ctx, n_steps)) || (rc = d_label.alloc(ctx, g->n_nodes))) return rc;
+        HIP_TRY(ctx, cl_copy_sync(ctx, d_nodes.p, g->path_nodes, n_steps * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, cl_copy_sync(ctx, d_label.p, g->label, g->n_nodes, hipMemcpyHostToDevice));
+    }
+    const uint64_t table_bytes = std::max<uint64_t>(g->n_nodes, 1) * sizeof(uint32_t);
+    for (size_t c0 = 0; c0 < todo.size();) {
+        // one chunk: up to kChunkPairs pairs whose first paths' tables fit in kChunkTableBytes (at least one first path)
+        std::vector<uint64_t> firsts;
+        size_t c1 = c0;
+        while (c1 < todo.size() && c1 - c0 < kChunkPairs) {
+            const uint64_t p = pairs[2 * todo[c1]];
+            if (firsts.empty() || firsts.back() != p) {
+                if (!firsts.empty() && (firsts.size() + 1) * table_bytes > kChunkTableBytes) break;
+                firsts.push_back(p);
+            }
+            ++c1;
+        }
+        DevBuf<uint32_t> d_tables, d_rep;
+        if ((rc = d_tables.alloc(ctx, firsts.size() * (table_bytes / sizeof(uint32_t))))) return rc;
+        if ((rc = d_rep.alloc(ctx, firsts.size()))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_rep.p, 0, firsts.size() * sizeof(uint32_t), ctx->stream));
+        for (size_t f = 0; f < firsts.size(); ++f)
+            HIP_TRY(ctx, cl_launch_induced_table(d_nodes.p + g->path_off[firsts[f]], g->path_off[firsts[f] + 1] - g->path_off[firsts[f]],
+                                                 d_tables.p + f * (table_bytes / sizeof(uint32_t)), g->n_nodes, d_rep.p + f, ctx->stream));
+        InducedChunk chunk{{}, {}, d_nodes.p, n_steps, d_label.p, d_tables.p};
+        for (size_t t = c0, f = 0; t < c1; ++t) {
+            const uint64_t k = todo[t], a = pairs[2 * k], b = pairs[2 * k + 1];
+            while (firsts[f] != a) ++f;
+            if (ids_bad(b)) continue;   // decided on the host (after the device's repeat check)
+            chunk.jobs.push_back(ClInducedJob{g->path_off[a], g->path_off[a + 1] - g->path_off[a], g->path_off[b], g->path_off[b + 1] - g->path_off[b],
+                                              f * (table_bytes / sizeof(uint32_t)), 0, 0});
+            chunk.job_pair.push_back(k);
+        }
+        if ((rc = pass(chunk))) return rc;
+        std::vector<uint32_t> rep(firsts.size());
+        HIP_TRY(ctx, cl_copy_sync(ctx, rep.data(), d_rep.p, rep.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t f = 0; f < firsts.size(); ++f) repeated[firsts[f]] |= rep[f] != 0;
+        c0 = c1;
+    }
+    for (uint64_t k = 0; k < n_pairs; ++k) {   // the first failing pair decides
+        int e = pre[k];
+        if (e == CL_OK && repeated[pairs[2 * k]]) e = CL_ERR_CYCLIC_GRAPH;
+        if (e == CL_OK && ids_bad(pairs[2 * k + 1])) e = CL_ERR_INVALID_ARGUMENT;
+        if (e != CL_OK) {
+            cl_set_error(ctx, "induced pairwise alignment of paths %llu and %llu (pair %llu): %s", (unsigned long long)pairs[2 * k],
+                         (unsigned long long)pairs[2 * k + 1], (unsigned long long)k, e == CL_ERR_CYCLIC_GRAPH ? "the first path follows a cycle" : "invalid path");
+            return e;
+        }
+    }
+    return CL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -403,76 +500,16 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* g, const ui
     cl_bind_device(ctx);
     if (!ctx || !g || (n_pairs && !pairs) || !text_out || !offsets_out) return CL_ERR_INVALID_ARGUMENT;
     *text_out = nullptr;
-    // what the host decides (cl_induced_pairwise_cigar's order): a path index out of range, then a path-1 node id out of range; a repeated path-1
-    // node is found on the device; then a path-2 node id out of range
-    std::vector<int8_t> bad_ids(g->n_paths, -1);
-    auto ids_bad = [&](uint64_t p) {
-        if (bad_ids[p] < 0) {
-            bad_ids[p] = 0;
-            for (uint64_t i = g->path_off[p]; i < g->path_off[p + 1]; ++i) if (g->path_nodes[i] >= g->n_nodes) { bad_ids[p] = 1; break; }
-            if (g->path_off[p + 1] - g->path_off[p] >= 0xFFFFFFFFull) bad_ids[p] = 1;   // positions are 32-bit words in the table
-        }
-        return bad_ids[p] == 1;
-    };
-    std::vector<int> pre(n_pairs, CL_OK);
-    std::vector<uint64_t> todo;   // pairs whose path 1 gets a position table, ordered by path 1
-    for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t a = pairs[2 * k], b = pairs[2 * k + 1];
-        if (a >= g->n_paths || b >= g->n_paths) { pre[k] = CL_ERR_INVALID_ARGUMENT; continue; }
-        if (ids_bad(a)) { pre[k] = CL_ERR_CYCLIC_GRAPH; continue; }
-        todo.push_back(k);
-    }
-    std::stable_sort(todo.begin(), todo.end(), [&](uint64_t x, uint64_t y) { return pairs[2 * x] < pairs[2 * y]; });
-    std::vector<uint8_t> repeated(g->n_paths, 0);
     std::vector<std::string> texts(n_pairs);
-    const uint64_t n_steps = g->path_off[g->n_paths];
-    DevBuf<uint32_t> d_nodes;
-    DevBuf<uint8_t> d_label;
-    int rc;
-    if (!todo.empty()) {
-        if ((rc = d_nodes.alloc(ctx, n_steps)) || (rc = d_label.alloc(ctx, g->n_nodes))) return rc;
-        HIP_TRY(ctx, cl_copy_sync(ctx, d_nodes.p, g->path_nodes, n_steps * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, cl_copy_sync(ctx, d_label.p, g->label, g->n_nodes, hipMemcpyHostToDevice));
-    }
-    const uint64_t table_bytes = std::max<uint64_t>(g->n_nodes, 1) * sizeof(uint32_t);
-    for (size_t c0 = 0; c0 < todo.size();) {
-        // one chunk: up to kChunkPairs pairs whose first paths' tables fit in kChunkTableBytes (at least one first path)
-        std::vector<uint64_t> firsts;
-        size_t c1 = c0;
-        while (c1 < todo.size() && c1 - c0 < kChunkPairs) {
-            const uint64_t p = pairs[2 * todo[c1]];
-            if (firsts.empty() || firsts.back() != p) {
-                if (!firsts.empty() && (firsts.size() + 1) * table_bytes > kChunkTableBytes) break;
-                firsts.push_back(p);
-            }
-            ++c1;
-        }
-        DevBuf<uint32_t> d_tables, d_rep;
-        if ((rc = d_tables.alloc(ctx, firsts.size() * (table_bytes / sizeof(uint32_t))))) return rc;
-        if ((rc = d_rep.alloc(ctx, firsts.size()))) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(d_rep.p, 0, firsts.size() * sizeof(uint32_t), ctx->stream));
-        for (size_t f = 0; f < firsts.size(); ++f)
-            HIP_TRY(ctx, cl_launch_induced_table(d_nodes.p + g->path_off[firsts[f]], g->path_off[firsts[f] + 1] - g->path_off[firsts[f]],
-                                                 d_tables.p + f * (table_bytes / sizeof(uint32_t)), g->n_nodes, d_rep.p + f, ctx->stream));
-        std::vector<ClInducedJob> jobs;
-        std::vector<uint64_t> job_pair;
-        for (size_t t = c0, f = 0; t < c1; ++t) {
-            const uint64_t k = todo[t], a = pairs[2 * k], b = pairs[2 * k + 1];
-            while (firsts[f] != a) ++f;
-            if (ids_bad(b)) continue;   // decided on the host (after the device's repeat check)
-            jobs.push_back(ClInducedJob{g->path_off[a], g->path_off[a + 1] - g->path_off[a], g->path_off[b], g->path_off[b + 1] - g->path_off[b],
-                                        f * (table_bytes / sizeof(uint32_t)), 0, 0});
-            job_pair.push_back(k);
-        }
+    int rc = induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
+        std::vector<ClInducedJob>& jobs = c.jobs;
+        int rc;
         DevBuf<ClInducedJob> d_jobs;
         DevBuf<int64_t> d_len;
         std::vector<int64_t> len(jobs.size());
         if ((rc = d_jobs.upload(ctx, jobs)) || (rc = d_len.alloc(ctx, jobs.size()))) return rc;
-        HIP_TRY(ctx, cl_launch_induced_runs(false, d_jobs.p, (uint32_t)jobs.size(), d_nodes.p, n_steps, d_label.p, g->n_nodes, d_tables.p, d_len.p, nullptr, ctx->stream));
-        std::vector<uint32_t> rep(firsts.size());
-        HIP_TRY(ctx, cl_copy_sync(ctx, rep.data(), d_rep.p, rep.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, cl_launch_induced_runs(false, d_jobs.p, (uint32_t)jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, d_len.p, nullptr, ctx->stream));
         HIP_TRY(ctx, cl_copy_sync(ctx, len.data(), d_len.p, len.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (size_t f = 0; f < firsts.size(); ++f) repeated[firsts[f]] |= rep[f] != 0;
         // write passes over groups of jobs whose text fits in kChunkTextBytes (at least one job)
         for (size_t w0 = 0; w0 < jobs.size();) {
             size_t w1 = w0;
@@ -487,23 +524,14 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* g, const ui
             std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
             std::vector<char> host(bytes);
             if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_text.alloc(ctx, bytes))) return rc;
-            HIP_TRY(ctx, cl_launch_induced_runs(true, d_jobs.p, (uint32_t)sub.size(), d_nodes.p, n_steps, d_label.p, g->n_nodes, d_tables.p, nullptr, d_text.p, ctx->stream));
+            HIP_TRY(ctx, cl_launch_induced_runs(true, d_jobs.p, (uint32_t)sub.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, nullptr, d_text.p, ctx->stream));
             HIP_TRY(ctx, cl_copy_sync(ctx, host.data(), d_text.p, bytes, hipMemcpyDeviceToHost));
-            for (size_t j = w0; j < w1; ++j) texts[job_pair[j]].assign(host.data() + jobs[j].text_off, (size_t)jobs[j].text_cap);
+            for (size_t j = w0; j < w1; ++j) texts[c.job_pair[j]].assign(host.data() + jobs[j].text_off, (size_t)jobs[j].text_cap);
             w0 = w1;
         }
-        c0 = c1;
-    }
-    for (uint64_t k = 0; k < n_pairs; ++k) {   // the first failing pair decides
-        int e = pre[k];
-        if (e == CL_OK && repeated[pairs[2 * k]]) e = CL_ERR_CYCLIC_GRAPH;
-        if (e == CL_OK && ids_bad(pairs[2 * k + 1])) e = CL_ERR_INVALID_ARGUMENT;
-        if (e != CL_OK) {
-            cl_set_error(ctx, "induced pairwise alignment of paths %llu and %llu (pair %llu): %s", (unsigned long long)pairs[2 * k],
-                         (unsigned long long)pairs[2 * k + 1], (unsigned long long)k, e == CL_ERR_CYCLIC_GRAPH ? "the first path follows a cycle" : "invalid path");
-            return e;
-        }
-    }
+        return CL_OK;
+    });
+    if (rc) return rc;
     uint64_t total = 0;
     for (uint64_t k = 0; k < n_pairs; ++k) { offsets_out[k] = total; total += texts[k].size(); }
     offsets_out[n_pairs] = total;
@@ -513,6 +541,22 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* g, const ui
     out[total] = '\0';
     *text_out = out;
     return CL_OK;
+}
+
+int cl_induced_pairwise_stats(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, cl_pair_stats* out) {
+    cl_bind_device(ctx);
+    if (!ctx || !g || (n_pairs && (!pairs || !out))) return CL_ERR_INVALID_ARGUMENT;
+    return induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
+        int rc;
+        DevBuf<ClInducedJob> d_jobs;
+        DevBuf<cl_pair_stats> d_stats;
+        std::vector<cl_pair_stats> stats(c.jobs.size());
+        if ((rc = d_jobs.upload(ctx, c.jobs)) || (rc = d_stats.alloc(ctx, c.jobs.size()))) return rc;
+        HIP_TRY(ctx, cl_launch_induced_stats(d_jobs.p, (uint32_t)c.jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, d_stats.p, ctx->stream));
+        HIP_TRY(ctx, cl_copy_sync(ctx, stats.data(), d_stats.p, stats.size() * sizeof(cl_pair_stats), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < stats.size(); ++j) out[c.job_pair[j]] = stats[j];
+        return CL_OK;
+    });
 }
 
 }  // extern "C"

@@ -367,6 +367,9 @@ struct ClInducedJob { uint64_t off1, n1, off2, n2, table, text_off, text_cap; };
 hipError_t cl_launch_induced_table(const uint32_t* p1, uint64_t n1, uint32_t* pos, uint64_t n_nodes, uint32_t* repeated, hipStream_t stream);
 hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
                                   uint64_t n_nodes, const uint32_t* tables, int64_t* text_len, char* text, hipStream_t stream);
+// the statistics of the same alignments (cl_induced_pairwise_stats): one pass, stats[j] for job j; text_off / text_cap are not read
+hipError_t cl_launch_induced_stats(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                   const uint32_t* tables, cl_pair_stats* stats, hipStream_t stream);
 
 // subaln_kernels.hip: the -s lines of one merge (cl_subaln_api.cpp).  One side of the merge on the device: the per-node step table
 // ((path << 32) | step of the node's first occurrence, UINT64_MAX: on no path), the labels, and the path names back to back

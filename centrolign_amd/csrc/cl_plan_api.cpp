@@ -792,11 +792,13 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
     const uint64_t root = n_slots - 1;
     // Core::output_pairwise_alignments (src/core.cpp:523-591): the file of pair (p1, p2) of the root's paths, '/' in the names read as '_'
     const bool induced = params->induced_pairwise_prefix && *params->induced_pairwise_prefix;
+    auto induced_name = [&](uint64_t p) {
+        std::string nm = fa.names[paths[root][p]];
+        std::replace(nm.begin(), nm.end(), '/', '_');
+        return nm;
+    };
     auto induced_file = [&](uint64_t p1, uint64_t p2, const char* suffix) {
-        std::string n1 = fa.names[paths[root][p1]], n2 = fa.names[paths[root][p2]];
-        std::replace(n1.begin(), n1.end(), '/', '_');
-        std::replace(n2.begin(), n2.end(), '/', '_');
-        return std::string(params->induced_pairwise_prefix) + "_" + n1 + "_" + n2 + suffix;
+        return std::string(params->induced_pairwise_prefix) + "_" + induced_name(p1) + "_" + induced_name(p2) + suffix;
     };
     if (induced) {   // output_pairwise_alignments(false): from the acyclic root graph, before the bonds are applied (core.cpp:82-85)
         cl_base_graph g;
@@ -819,6 +821,37 @@ int cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const ch
         }
         free(text);
         if (rc) return fail(rc);
+    }
+    if (params->pair_stats_path && *params->pair_stats_path) {   // this project's --pair-stats: the same graph, pairs, order and names as the .txt files above
+        cl_base_graph g;
+        cl_owned_base_graph_view(graph[root], &g);
+        std::vector<uint64_t> pairs;
+        for (uint64_t p1 = 0; p1 < g.n_paths; ++p1)
+            for (uint64_t p2 = p1 + 1; p2 < g.n_paths; ++p2) { pairs.push_back(p1); pairs.push_back(p2); }
+        const uint64_t n_pairs = pairs.size() / 2;
+        std::vector<cl_pair_stats> ps(n_pairs);
+        std::vector<double> dist(g.n_paths * g.n_paths);
+        if ((rc = cl_induced_pairwise_stats(ctx, &g, pairs.data(), n_pairs, ps.data())) || (rc = cl_alignment_distances(ps.data(), g.n_paths, dist.data()))) {
+            cl_set_error(ctx, "pairwise statistics of the root graph failed");
+            return fail(rc);
+        }
+        std::string tsv = "sample1\tsample2\tmatches\tmismatches\tinsertions\tdeletions\tmatch_runs\tmismatch_runs\tinsertion_runs\tdeletion_runs\tdistance\n";
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const uint64_t p1 = pairs[2 * k], p2 = pairs[2 * k + 1];
+            const cl_pair_stats& s = ps[k];
+            char num[256];
+            snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.9g\n", (unsigned long long)s.eq, (unsigned long long)s.x,
+                     (unsigned long long)s.ins, (unsigned long long)s.del, (unsigned long long)s.eq_runs, (unsigned long long)s.x_runs,
+                     (unsigned long long)s.ins_runs, (unsigned long long)s.del_runs, dist[p1 * g.n_paths + p2]);
+            tsv += induced_name(p1);
+            tsv += '\t';
+            tsv += induced_name(p2);
+            tsv += num;
+        }
+        std::ofstream out(params->pair_stats_path, std::ios::binary);
+        if (out) out.write(tsv.data(), (std::streamsize)tsv.size());
+        out.close();
+        if (!out) { cl_set_error(ctx, "could not write the pairwise statistics to %s", params->pair_stats_path); return fail(CL_ERR_INVALID_ARGUMENT); }
     }
     if (cyclize && !bond_alns.empty()) {   // Core::apply_bonds (src/core.cpp:594-648)
         const auto tc = now();

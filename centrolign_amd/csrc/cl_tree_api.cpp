@@ -3,6 +3,8 @@
 // into a distance, then on the host: neighbor joining (Saitou-Nei with the Studier-Keppler Q), a midpoint root and the Newick text in the
 // style of Tree::to_newick (src/tree.cpp:615-645).  Every number and tie-break is fixed so that a few lines of Python restate the result
 // bit for bit: this file is built without fused multiply-adds (Makefile, FPOFF), sums run in the order written here.
+// Also here: the distances an alignment implies (cl_alignment_distances over cl_induced_pairwise_stats) and the loop that rebuilds the guide tree
+// from them (cl_refine_guide_tree).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -289,6 +291,98 @@ int cl_infer_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_
     cl_kmer_distances_free(&d);
     if (rc) cl_set_error(ctx, "%s", cl_last_error(nullptr));
     return rc;
+}
+
+// 1 - 2 eq / (2 eq + 2 x + ins + del): the share of the two sequences' bases outside '=' columns (this project's definition; header)
+int cl_alignment_distances(const cl_pair_stats* stats, uint64_t n, double* distance_out) {
+    if (!stats || !distance_out || n < 2) return CL_ERR_INVALID_ARGUMENT;
+    uint64_t k = 0;
+    for (uint64_t a = 0; a < n; ++a) {
+        distance_out[a * n + a] = 0.0;
+        for (uint64_t b = a + 1; b < n; ++b, ++k) {
+            const uint64_t eq2 = 2 * stats[k].eq, den = eq2 + 2 * stats[k].x + stats[k].ins + stats[k].del;
+            const double d = eq2 == den || den == 0 ? 0.0 : 1.0 - (double)eq2 / (double)den;
+            distance_out[a * n + b] = distance_out[b * n + a] = d;
+        }
+    }
+    return CL_OK;
+}
+
+int cl_refine_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const char* newick, const cl_msa_params* params, int max_rounds,
+                         char** newick_out, uint64_t* len_out, int* rounds_run_out, int* converged_out) {
+    cl_bind_device(ctx);
+    if (newick_out) *newick_out = nullptr;
+    if (len_out) *len_out = 0;
+    if (rounds_run_out) *rounds_run_out = 0;
+    if (converged_out) *converged_out = 0;
+    if (!ctx || !fasta_text || !params || !newick_out) { cl_set_error(ctx, "null argument"); return CL_ERR_INVALID_ARGUMENT; }
+    if (max_rounds < 1) { cl_set_error(ctx, "cl_refine_guide_tree needs at least one round, got %d", max_rounds); return CL_ERR_INVALID_ARGUMENT; }
+    cl_fasta fa;
+    int rc = cl_parse_fasta(ctx, fasta_text, fasta_len, &fa);
+    if (rc) return rc;
+    struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
+    const uint64_t n = fa.n_sequences;
+    if (n < 2) { cl_set_error(ctx, "FASTA input contains %llu sequence(s), cannot form an alignment", (unsigned long long)n); return CL_ERR_INVALID_ARGUMENT; }
+    bool have_tree = newick != nullptr;   // false: the in-order tree, which has no text here
+    std::string current = newick ? newick : "";
+    cl_msa_params mp = *params;   // the alignment of a round writes nothing but its GFA
+    mp.subproblems_prefix = mp.induced_pairwise_prefix = mp.subalignments_path = mp.bonds_prefix = mp.pair_stats_path = nullptr;
+    mp.restart = 0;
+    mp.cyclize = 0;
+    mp.force_gfa_output = 1;
+    int rounds = 0, converged = 0;
+    while (n >= 3 && rounds < max_rounds && !converged) {
+        char* text = nullptr;
+        uint64_t len = 0;
+        if ((rc = cl_msa(ctx, fasta_text, fasta_len, have_tree ? current.c_str() : nullptr, &mp, &text, &len, nullptr))) return rc;
+        cl_owned_base_graph* owned = nullptr;
+        char** path_names = nullptr;
+        uint64_t n_paths = 0;
+        rc = cl_read_gfa(text, len, 1, &owned, &path_names, &n_paths);
+        free(text);
+        if (rc) { cl_set_error(ctx, "cannot read back the alignment of refinement round %d", rounds + 1); return rc; }
+        std::vector<uint64_t> seq_of(n_paths, n);   // path -> FASTA index
+        for (uint64_t p = 0; p < n_paths; ++p) {
+            for (uint64_t q = 0; q < n && seq_of[p] == n; ++q) if (strcmp(fa.names[q], path_names[p]) == 0) seq_of[p] = q;
+            free(path_names[p]);
+        }
+        free(path_names);
+        struct FreeGraph { cl_owned_base_graph* g; ~FreeGraph() { cl_owned_base_graph_free(g); } } free_graph{owned};
+        if (n_paths != n || std::set<uint64_t>(seq_of.begin(), seq_of.end()).size() != n || *std::max_element(seq_of.begin(), seq_of.end()) >= n) {
+            cl_set_error(ctx, "the alignment of refinement round %d does not hold every sequence once", rounds + 1);
+            return CL_ERR_INVALID_ARGUMENT;
+        }
+        cl_base_graph g;
+        cl_owned_base_graph_view(owned, &g);
+        std::vector<uint64_t> pairs;
+        for (uint64_t p = 0; p < n; ++p)
+            for (uint64_t q = p + 1; q < n; ++q) { pairs.push_back(p); pairs.push_back(q); }
+        std::vector<cl_pair_stats> stats(pairs.size() / 2);
+        if ((rc = cl_induced_pairwise_stats(ctx, &g, pairs.data(), stats.size(), stats.data()))) return rc;
+        std::vector<double> by_path(n * n), by_seq(n * n);
+        if ((rc = cl_alignment_distances(stats.data(), n, by_path.data()))) return rc;
+        for (uint64_t p = 0; p < n; ++p)
+            for (uint64_t q = 0; q < n; ++q) by_seq[seq_of[p] * n + seq_of[q]] = by_path[p * n + q];
+        char* tree = nullptr;
+        uint64_t tree_len = 0;
+        if ((rc = cl_neighbor_joining_newick(by_seq.data(), n, fa.names, &tree, &tree_len))) { cl_set_error(ctx, "%s", cl_last_error(nullptr)); return rc; }
+        const std::string next(tree, tree_len);
+        free(tree);
+        ++rounds;
+        converged = have_tree && next == current;
+        current = next;
+        have_tree = true;
+    }
+    if (have_tree) {
+        char* out = (char*)malloc(current.size() + 1);
+        if (!out) return CL_ERR_OUT_OF_MEMORY;
+        memcpy(out, current.c_str(), current.size() + 1);
+        *newick_out = out;
+        if (len_out) *len_out = current.size();
+    }
+    if (rounds_run_out) *rounds_run_out = rounds;
+    if (converged_out) *converged_out = converged;
+    return CL_OK;
 }
 
 }  // extern "C"

@@ -18,6 +18,11 @@
 //
 // One 1024-thread workgroup per pair walks path 2 in tiles of 4096 steps (4 consecutive steps per thread, two block scans per tile, carries in
 // registers).  The gather through pos1 is the only random access; path 2, and path 1 at the emitted indices, stream.
+//
+// cl_induced_pairwise_stats (induced_stats_kernel) wants the same alignment as numbers: per op the bases and the number of runs.  Scan 1 and the
+// tokens are the same; scan 2's monoid becomes (bases per op, runs per op, first op, last op) of a token segment, joined with the run that spans
+// the seam counted once.  Only the whole pair's element is wanted, so a tile is reduced in order rather than scanned, in one pass: nothing is
+// stored per step and no text exists; each pair's eight counters are written once at the end.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -159,6 +164,66 @@ struct RunBuilder {
     }
 };
 
+// cl_induced_pairwise_stats' element of a token segment: bases and runs per op (indexed by kOpEq .. kOpI), the segment's first and last op
+// (kOpNone: no token).  Also the builder: tokens are appended with operator().
+struct StatScan {
+    int64_t n[4], runs[4];
+    uint32_t first, last;
+    static __device__ StatScan ident() { return {{0, 0, 0, 0}, {0, 0, 0, 0}, kOpNone, kOpNone}; }
+    __device__ StatScan down(unsigned d) const {
+        StatScan o;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            o.n[k] = (int64_t)__shfl_down((long long)n[k], d, 64);
+            o.runs[k] = (int64_t)__shfl_down((long long)runs[k], d, 64);
+        }
+        o.first = (uint32_t)__shfl_down((int)first, d, 64);
+        o.last = (uint32_t)__shfl_down((int)last, d, 64);
+        return o;
+    }
+    __device__ void operator()(uint32_t op, int64_t cnt) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            n[k] += op == k ? cnt : 0;
+            runs[k] += op == k && op != last;
+        }
+        if (first == kOpNone) first = op;
+        last = op;
+    }
+};
+__device__ __forceinline__ StatScan combine(const StatScan& a, const StatScan& b) {
+    StatScan r;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        r.n[k] = a.n[k] + b.n[k];
+        r.runs[k] = a.runs[k] + b.runs[k] - (a.last == k && b.first == k);   // one run across the seam
+    }
+    r.first = a.first != kOpNone ? a.first : b.first;
+    r.last = b.last != kOpNone ? b.last : a.last;
+    return r;
+}
+
+// the workgroup's elements combined in thread order; the result is thread 0's alone.  lds: kWaves entries, free to reuse after the next barrier
+__device__ __forceinline__ StatScan block_reduce_ordered(StatScan v, StatScan* lds) {
+    const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const StatScan o = v.down(d);
+        if (lane + d < 64) v = combine(v, o);
+    }
+    if (lane == 0) lds[w] = v;
+    __syncthreads();
+    if (w == 0) {
+        v = lane < kWaves ? lds[lane] : StatScan::ident();
+#pragma unroll
+        for (unsigned d = 1; d < kWaves; d <<= 1) {
+            const StatScan o = v.down(d);
+            if (lane + d < kWaves) v = combine(v, o);
+        }
+    }
+    return v;
+}
+
 // the same tokens continuing the absolute state p (p.last, p.last_op: the run in progress; p.text: its text offset): a finished run is written out
 struct RunWriter {
     RunScan p;
@@ -249,6 +314,53 @@ __global__ void __launch_bounds__(kThreads) induced_runs_kernel(const ClInducedJ
     }
 }
 
+// One pass: scan 1 as above, then every thread's tokens go into one StatScan, the tile is reduced in order and thread 0 appends it to the pair's
+// element, which it keeps in registers.  (lds2 is written again only after the barriers of the next tile's scan 1, which wave 0 reaches after its reads.)
+__global__ void __launch_bounds__(kThreads) induced_stats_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                                const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                                cl_pair_stats* __restrict__ stats) {
+    __shared__ MatchScan lds1[kWaves];
+    __shared__ StatScan lds2[kWaves];
+    const ClInducedJob job = jobs[blockIdx.x];
+    const uint32_t* pos = tables + job.table;
+    PairView v{path_nodes + job.off1, path_nodes + job.off2, path_nodes + n_steps, label, n_nodes, (int64_t)job.n1, (int64_t)job.n2};
+    MatchScan c1 = MatchScan::ident();
+    StatScan c2 = StatScan::ident();
+    for (int64_t base = 0; base < v.n2; base += kTile) {
+        const int64_t s0 = base + (int64_t)threadIdx.x * kItems;
+        uint32_t a[kItems];
+        MatchScan agg = MatchScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            a[r] = kNoPos;
+            if (s0 + r < v.n2) a[r] = pos[v.p2[s0 + r]];
+            if (a[r] != kNoPos) agg = combine(agg, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        MatchScan tot1;
+        MatchScan x = combine(c1, block_exclusive(agg, lds1, tot1));
+        c1 = combine(c1, tot1);
+        StatScan sagg = StatScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            if (a[r] == kNoPos) continue;
+            match_tokens(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt) { sagg(op, cnt); });
+            x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        const StatScan tile = block_reduce_ordered(sagg, lds2);
+        if (threadIdx.x == 0) c2 = combine(c2, tile);   // the pair's element lives in thread 0 alone
+    }
+    if (threadIdx.x != 0) return;
+    // the run after the last match, as in induced_runs_kernel
+    const int64_t k = c1.cnt;
+    const int64_t e_last = k > 0 ? k - 1 + (c1.best > 0 ? c1.best : 0) : -1;
+    const int64_t g2 = v.n1 > e_last + 1 ? v.n1 - e_last - 1 : 0, g1 = v.n2 - 1 - c1.last;
+    gap_run_tokens(v, e_last, c1.last, g1, g2, [&](uint32_t op, int64_t cnt) { c2(op, cnt); });
+    cl_pair_stats out;
+    out.eq = (uint64_t)c2.n[kOpEq]; out.x = (uint64_t)c2.n[kOpX]; out.ins = (uint64_t)c2.n[kOpI]; out.del = (uint64_t)c2.n[kOpD];
+    out.eq_runs = (uint64_t)c2.runs[kOpEq]; out.x_runs = (uint64_t)c2.runs[kOpX]; out.ins_runs = (uint64_t)c2.runs[kOpI]; out.del_runs = (uint64_t)c2.runs[kOpD];
+    stats[blockIdx.x] = out;
+}
+
 // pos[path1[i]] = i; a node met twice leaves one of its positions behind, which the check reads back
 __global__ void induced_scatter_kernel(const uint32_t* __restrict__ p1, uint64_t n1, uint32_t* __restrict__ pos) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * blockDim.x) pos[p1[i]] = (uint32_t)i;
@@ -274,5 +386,12 @@ hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t
     if (n_jobs == 0) return hipSuccess;
     if (write) hipLaunchKernelGGL(induced_runs_kernel<true>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, text_len, text);
     else hipLaunchKernelGGL(induced_runs_kernel<false>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, text_len, text);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_stats(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                   const uint32_t* tables, cl_pair_stats* stats, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(induced_stats_kernel, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, stats);
     return hipGetLastError();
 }

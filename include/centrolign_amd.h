@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 15   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 16   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -646,6 +646,19 @@ int cl_induced_pairwise_cigar(const cl_base_graph* graph, uint64_t path1, uint64
  * Byte for byte what cl_induced_pairwise_cigar returns for each pair; the error code is the one it returns for the first failing pair.
  * Device memory beyond the graph's paths and labels: at most 256 MB of position tables and 256 MB of CIGAR text (or one pair's CIGAR) at a time. */
 int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, char** text_out, uint64_t* offsets_out);
+/* The same alignment as numbers: what parsing the text of cl_induced_pairwise_cigar(graph, path1, path2) gives — per letter the sum of its run
+ * lengths (eq, x, ins, del) and the number of runs that carry it (*_runs) — without the text ever being made.  eq + x + del is the length of
+ * path 1 and eq + x + ins that of path 2 wherever path 2 meets path 1's nodes in order.
+ * cl_induced_pairwise_stat: host only, the definition.  cl_induced_pairwise_stats: every (pairs[2k], pairs[2k+1]) in ONE device pass
+ * (induced_kernels.hip: no text, no per-step array; 64 bytes per pair come back); pairs may repeat, (p, p) is allowed.  Error codes as
+ * cl_induced_pairwise_cigar / cl_induced_pairwise_cigars: the code of the first failing pair (out is then unspecified).  Device memory beyond
+ * the graph's paths and labels: at most 256 MB of position tables at a time. */
+typedef struct cl_pair_stats {
+    uint64_t eq, x, ins, del;                        /* bases in '=', 'X', 'I', 'D' runs */
+    uint64_t eq_runs, x_runs, ins_runs, del_runs;    /* number of runs of each letter */
+} cl_pair_stats;
+int cl_induced_pairwise_stat(const cl_base_graph* graph, uint64_t path1, uint64_t path2, cl_pair_stats* out);
+int cl_induced_pairwise_stats(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, cl_pair_stats* out /* [n_pairs] */);
 /* The -A output of the CLI after cyclisation (src/core.cpp:537-545): output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), graph,
  * path1, path2) (src/alignment.cpp:569-904) — blocks of colinear alignment between the two paths of a graph that may have cycles; name1 / name2
  * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
@@ -847,6 +860,11 @@ typedef struct cl_msa_params {
     const char*     bonds_prefix;            /* --bond-prefix: with -c, PREFIX_<sequence>_cigar_<k>.txt for the k-th bond alignment found in that
                                                 sequence (cl_bond_alignment_cigar); nothing when the bonds come from a restart.  NULL: off */
     int             force_gfa_output;        /* --force-gfa-output: the GFA of the root even for two sequences (src/main.cpp:290-301) */
+    const char*     pair_stats_path;         /* --pair-stats (this project's): a TSV file with cl_induced_pairwise_stats and the cl_alignment_distances
+                                                distance of every pair (p, q), p < q, of the root graph's paths — the graph, order and names of the
+                                                -A .txt files (before the bonds of -c are applied).  Header: sample1 sample2 matches mismatches insertions
+                                                deletions match_runs mismatch_runs insertion_runs deletion_runs distance; integers as they are, the
+                                                distance as %.9g.  One device call for all pairs.  NULL: off */
 } cl_msa_params;
 void cl_msa_params_default(cl_msa_params* p);
 typedef struct cl_msa_stats {
@@ -872,7 +890,17 @@ int  cl_msa(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const c
  *   Newick text in the style of Tree::to_newick (src/tree.cpp:615-645): quoted leaf labels, ":%g" lengths on every non-root node, children in
  *   the order of their smallest FASTA index, ";" and no line end.  The distance matrix must be finite and symmetric with a zero diagonal;
  *   names must be distinct, non-empty and free of '"'.
- * cl_infer_guide_tree: cl_parse_fasta, cl_kmer_distances_compute, cl_neighbor_joining_newick.  Text returned through char** is malloc'ed. */
+ * cl_infer_guide_tree: cl_parse_fasta, cl_kmer_distances_compute, cl_neighbor_joining_newick.  Text returned through char** is malloc'ed.
+ * cl_alignment_distances: host only.  stats[] holds the pairs (a, b), a < b, of n paths with a as the outer loop (n * (n - 1) / 2 entries).  With
+ *   den = 2 * eq + 2 * x + ins + del (the two path lengths added, in 64-bit integers): distance[a][b] = distance[b][a] = +0 when 2 * eq == den or
+ *   den == 0, otherwise 1.0 - (double)(2 * eq) / (double)den in doubles; the diagonal is 0.  n >= 2.  This is this project's definition of an
+ *   alignment distance (the share of the two sequences' bases that are not in an '=' column); the reference has none.
+ * cl_refine_guide_tree: the classic remedy of progressive aligners — align, take distances from the alignment, rebuild the tree, align again.
+ *   One round: cl_msa under the current tree (params' scoring, budget, workers, devices and calibration switches; every side output — -S, -R, -A,
+ *   -s, bond prefix, pair stats — and cyclize forced off, GFA output forced on), cl_read_gfa, cl_induced_pairwise_stats of all pairs,
+ *   cl_alignment_distances permuted to FASTA order, cl_neighbor_joining_newick with the FASTA names.  A round whose tree equals, as text, the tree
+ *   it ran under sets *converged_out = 1 and ends the loop; otherwise its tree is the next round's, for at most max_rounds (>= 1) rounds.  With
+ *   fewer than three sequences no round runs: *newick_out is a copy of newick (NULL when newick is NULL: the in-order tree).  Deterministic. */
 typedef struct cl_kmer_distances {
     uint64_t  n;
     int       k;
@@ -885,6 +913,10 @@ int  cl_kmer_distances_compute(cl_context* ctx, const char* const* sequences, co
 void cl_kmer_distances_free(cl_kmer_distances* d);
 int  cl_neighbor_joining_newick(const double* distance, uint64_t n, const char* const* names, char** newick_out, uint64_t* len_out /* may be NULL */);
 int  cl_infer_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, int k, char** newick_out, uint64_t* len_out /* may be NULL */);
+int  cl_alignment_distances(const cl_pair_stats* stats /* [n*(n-1)/2] */, uint64_t n, double* distance_out /* [n*n] */);
+int  cl_refine_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const char* newick /* NULL: in-order */, const cl_msa_params* params,
+                          int max_rounds, char** newick_out, uint64_t* len_out /* may be NULL */, int* rounds_run_out /* may be NULL */,
+                          int* converged_out /* may be NULL */);
 
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
