@@ -674,6 +674,7 @@ __global__ void __launch_bounds__(256) far_merge_kernel(ClChainDevice D, const i
 // ---- host entry points ---------------------------------------------------------------------------------------------------
 hipError_t cl_chain_far_init(const ClChainDevice& D, const uint32_t* d_base, uint32_t max_padded, uint32_t r_pad, int32_t sig_bias, uint32_t band_shift,
                              uint32_t off_bits, uint32_t* key_off, uint32_t* key_band, uint32_t* idx, hipStream_t stream) {
+    // (grid.y = combinations: the far pass runs beside the walk kernels only, 768 combinations at most — far below the 65 535 a launch dimension takes)
     hipLaunchKernelGGL(far_init_kernel, dim3((max_padded + 255) / 256, D.n_combos), dim3(256), 0, stream, D.combos, d_base, D.n_combos, r_pad,
                        sig_bias, band_shift, off_bits, D.far_rec, key_off, key_band, idx);
     return hipGetLastError();
@@ -743,6 +744,7 @@ hipError_t cl_peer_store_word(uint32_t* where, uint32_t value, hipStream_t strea
 }
 
 hipError_t cl_chain_far_merge(const ClChainDevice& D, const int* slot, uint32_t first, uint32_t count, uint32_t share_n, uint32_t share_i, hipStream_t stream) {
+    // (grid.y = combinations: the shared far pass only, kPeerMaxCombos at most)
     hipLaunchKernelGGL(far_merge_kernel, dim3((count * 7 + 255) / 256, D.n_combos), dim3(256), 0, stream, D, slot, first, count, share_n, share_i);
     return hipGetLastError();
 }

@@ -25,6 +25,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 
 #include "device_once.h"
 #include "chain_device.h"
@@ -87,8 +88,8 @@ __device__ __forceinline__ void lds_barrier() {
 // acc index layout: [0] gap-free, [1 + pw] tree pw (pw even: shift > query, pw odd: shift < query)
 // predecessors = the records of blocks [src_block_lo, src_block_hi)
 __global__ void __launch_bounds__(256) chain_inter_kernel(ClChainDevice D, uint32_t block_first, uint32_t block_count,
-                                                          uint32_t src_block_lo, uint32_t src_block_hi, uint32_t tile_recs) {
-    const ClChainCombo cb = D.combos[blockIdx.z];
+                                                          uint32_t src_block_lo, uint32_t src_block_hi, uint32_t tile_recs, uint32_t combo_base) {
+    const ClChainCombo cb = D.combos[combo_base + blockIdx.z];
     const uint32_t rec_lo = cb.prefix[src_block_lo] & ~D.lo_mask, rec_hi = cb.prefix[src_block_hi];
     const uint32_t tile0 = rec_lo + blockIdx.x * tile_recs;
     if (tile0 >= rec_hi) return;
@@ -136,8 +137,8 @@ __global__ void __launch_bounds__(256) chain_inter_kernel(ClChainDevice D, uint3
 // sparse_chain_dp (anchorer.hpp:1511-1750) has one gap-free tree per chain pair and no shift condition: a record is
 // (insertion index, offset, dp) and a query keeps ONE maximum.  Same tiling as chain_inter_kernel, a quarter of the work.
 __global__ void __launch_bounds__(256) chain_inter_sparse_kernel(ClChainDevice D, uint32_t block_first, uint32_t block_count,
-                                                                 uint32_t src_block_lo, uint32_t src_block_hi, uint32_t tile_recs) {
-    const ClChainCombo cb = D.combos[blockIdx.z];
+                                                                 uint32_t src_block_lo, uint32_t src_block_hi, uint32_t tile_recs, uint32_t combo_base) {
+    const ClChainCombo cb = D.combos[combo_base + blockIdx.z];
     const uint32_t rec_lo = cb.prefix[src_block_lo] & ~D.lo_mask, rec_hi = cb.prefix[src_block_hi];
     const uint32_t tile0 = rec_lo + blockIdx.x * tile_recs;
     if (tile0 >= rec_hi) return;
@@ -820,16 +821,20 @@ __global__ void __launch_bounds__(kChainMacro) chain_walk_fold_kernel(ClChainDev
 }
 
 // own_rec[c][s] = position of pair s's record in combination c (a pair has at most one record per combination)
-__global__ void __launch_bounds__(256) chain_own_rec_kernel(const ClChainCombo* combos) {
-    const ClChainCombo cb = combos[blockIdx.y];
+__global__ void __launch_bounds__(256) chain_own_rec_kernel(const ClChainCombo* combos, uint32_t combo_base) {
+    const ClChainCombo cb = combos[combo_base + blockIdx.y];
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     if (r < cb.n_recs) cb.own_rec[cb.rec_s[r]] = r;
 }
 
 hipError_t cl_chain_launch_own_rec(const ClChainDevice& D, uint32_t max_recs, hipStream_t stream) {
     if (max_recs == 0) return hipSuccess;
-    hipLaunchKernelGGL(chain_own_rec_kernel, dim3((max_recs + 255) / 256, D.n_combos), dim3(256), 0, stream, D.combos);
-    return hipGetLastError();
+    // (launched for the walk kernels only, which take 768 combinations at most: one launch today)
+    for (uint32_t c0 = 0; c0 < D.n_combos; c0 += kChainGridCombos) {
+        hipLaunchKernelGGL(chain_own_rec_kernel, dim3((max_recs + 255) / 256, std::min(kChainGridCombos, D.n_combos - c0)), dim3(256), 0, stream, D.combos, c0);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 // the query results of ONE pair in every combination (7 per combination), for a traceback that fetches rows as it goes instead of downloading
@@ -841,8 +846,8 @@ __global__ void __launch_bounds__(256) chain_acc_row_kernel(const ClChainCombo* 
 
 // the dense query tables out of their factors (cl_chain_api.cpp: factored queries): combination c = (tag1, tag2); fa_d == nullptr: the gap-free DP (no shifts)
 __global__ void __launch_bounds__(256) chain_expand_queries_kernel(const uint32_t* fa_qt, const uint32_t* fa_d, const uint32_t* fb_qoff, const uint32_t* fb_d,
-                                                                   const uint32_t* combo_tags, uint32_t n_pairs, uint32_t* qt, uint32_t* qoff, int32_t* q) {
-    const uint32_t c = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
+                                                                   const uint32_t* combo_tags, uint32_t n_pairs, uint32_t* qt, uint32_t* qoff, int32_t* q, uint32_t combo_base) {
+    const uint32_t c = combo_base + blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     if (s >= n_pairs) return;
     const size_t a = (size_t)combo_tags[2 * c] * n_pairs + s, b = (size_t)combo_tags[2 * c + 1] * n_pairs + s, at = (size_t)c * n_pairs + s;
     const uint32_t t = fa_qt[a];
@@ -855,8 +860,11 @@ __global__ void __launch_bounds__(256) chain_expand_queries_kernel(const uint32_
 hipError_t cl_chain_expand_queries(const uint32_t* fa_qt, const uint32_t* fa_d, const uint32_t* fb_qoff, const uint32_t* fb_d, const uint32_t* combo_tags, uint32_t n_combos,
                                    uint32_t n_pairs, uint32_t* qt, uint32_t* qoff, int32_t* q, hipStream_t stream) {
     if (n_combos == 0 || n_pairs == 0) return hipSuccess;
-    hipLaunchKernelGGL(chain_expand_queries_kernel, dim3((n_pairs + 255) / 256, n_combos), dim3(256), 0, stream, fa_qt, fa_d, fb_qoff, fb_d, combo_tags, n_pairs, qt, qoff, q);
-    return hipGetLastError();
+    for (uint32_t c0 = 0; c0 < n_combos; c0 += kChainGridCombos) {
+        hipLaunchKernelGGL(chain_expand_queries_kernel, dim3((n_pairs + 255) / 256, std::min(kChainGridCombos, n_combos - c0)), dim3(256), 0, stream, fa_qt, fa_d, fb_qoff, fb_d, combo_tags, n_pairs, qt, qoff, q, c0);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t cl_chain_acc_row(const ClChainDevice& D, uint32_t s, int* out, hipStream_t stream) {
@@ -896,9 +904,13 @@ hipError_t cl_chain_launch_inter(const ClChainDevice& D, uint32_t block_first, u
                                  uint32_t src_block_hi, uint32_t max_recs, uint32_t tile_recs, hipStream_t stream) {
     if (max_recs == 0) return hipSuccess;
     const uint32_t tiles = (max_recs + tile_recs - 1) / tile_recs;
-    if (D.sparse) hipLaunchKernelGGL(chain_inter_sparse_kernel, dim3(tiles, (block_count + 255) / 256, D.n_combos), dim3(256), 0, stream, D, block_first, block_count, src_block_lo, src_block_hi, tile_recs);
-    else hipLaunchKernelGGL(chain_inter_kernel, dim3(tiles, (block_count + 255) / 256, D.n_combos), dim3(256), 0, stream, D, block_first, block_count, src_block_lo, src_block_hi, tile_recs);
-    return hipGetLastError();
+    for (uint32_t c0 = 0; c0 < D.n_combos; c0 += kChainGridCombos) {
+        const dim3 grid(tiles, (block_count + 255) / 256, std::min(kChainGridCombos, D.n_combos - c0));
+        if (D.sparse) hipLaunchKernelGGL(chain_inter_sparse_kernel, grid, dim3(256), 0, stream, D, block_first, block_count, src_block_lo, src_block_hi, tile_recs, c0);
+        else hipLaunchKernelGGL(chain_inter_kernel, grid, dim3(256), 0, stream, D, block_first, block_count, src_block_lo, src_block_hi, tile_recs, c0);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 // ---- chaining DPs over MORE combinations than the walk kernels take (round 6) ---------------------------------------------------------------------------------
@@ -956,9 +968,9 @@ __global__ void __launch_bounds__(256) chain_group_store_kernel(ClChainDevice D,
     for (int k = 0; k < 7; ++k) cc.val[(size_t)k * cc.n_recs + pos] = v[k];
 }
 
-// the records of the pairs [s0, s1) of combination blockIdx.z against the queries of the pairs [s1 + 256 blockIdx.y, ...): tile blockIdx.x of 256 records
-__global__ void __launch_bounds__(256) chain_group_push_kernel(ClChainDevice D, uint32_t s0, uint32_t s1, uint32_t n_pairs) {
-    const ClChainCombo cb = D.combos[blockIdx.z];
+// the records of the pairs [s0, s1) of combination combo_base + blockIdx.z against the queries of the pairs [s1 + 256 blockIdx.y, ...): tile blockIdx.x of 256 records
+__global__ void __launch_bounds__(256) chain_group_push_kernel(ClChainDevice D, uint32_t s0, uint32_t s1, uint32_t n_pairs, uint32_t combo_base) {
+    const ClChainCombo cb = D.combos[combo_base + blockIdx.z];
     const uint32_t rec_lo = lower_bound_u32(cb.rec_s, cb.n_recs, s0), rec_hi = lower_bound_u32(cb.rec_s, cb.n_recs, s1);
     const uint32_t tile0 = rec_lo + blockIdx.x * 256;
     if (tile0 >= rec_hi) return;
@@ -1005,9 +1017,14 @@ hipError_t cl_chain_launch_group(const ClChainDevice& D, uint32_t s0, uint32_t s
     hipLaunchKernelGGL(chain_group_reduce_kernel, dim3(s1 - s0, (D.n_combos + 255) / 256), dim3(256), 0, stream, D, s0, s1, dp_enc);
     const uint32_t n_store = n_group_recs > s1 - s0 ? n_group_recs : s1 - s0;
     hipLaunchKernelGGL(chain_group_store_kernel, dim3((n_store + 255) / 256), dim3(256), 0, stream, D, s0, s1, dp_enc);
+    if (const hipError_t e = hipGetLastError()) return e;
     if (s1 < D.n_pairs && n_group_recs)
-        hipLaunchKernelGGL(chain_group_push_kernel, dim3((s1 - s0 + 255) / 256, (D.n_pairs - s1 + 255) / 256, D.n_combos), dim3(256), 0, stream, D, s0, s1, D.n_pairs);
-    return hipGetLastError();
+        for (uint32_t c0 = 0; c0 < D.n_combos; c0 += kChainGridCombos) {
+            hipLaunchKernelGGL(chain_group_push_kernel, dim3((s1 - s0 + 255) / 256, (D.n_pairs - s1 + 255) / 256, std::min(kChainGridCombos, D.n_combos - c0)), dim3(256), 0, stream, D, s0, s1,
+                               D.n_pairs, c0);
+            if (const hipError_t e = hipGetLastError()) return e;
+        }
+    return hipSuccess;
 }
 
 hipError_t cl_chain_launch_intra(const ClChainDevice& D, uint32_t block_first, uint32_t block_count, uint32_t near_blocks, hipStream_t stream) {

@@ -668,6 +668,8 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
     // intra kernel keeps in registers)
     std::vector<uint32_t> combo_of((size_t)n_tag[0] * n_tag[1], kNone);
     std::vector<Combo> combos;
+    const char* far_ran = "none";
+    bool par_numbering = false, walk_reduce = false;   // (for the CL_CHAIN_TIMING line that names the paths this DP took)
     std::vector<uint32_t> rec_off(M + 1, 0);
     ClRawVec<uint32_t> rec_combo, rec_pos;
     {
@@ -720,6 +722,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
         const size_t n_tags = combo_of.size();
         static const uint64_t par_min = [] { const char* e = getenv("CL_CHAIN_PAR_RECORDS_MIN"); return e ? (uint64_t)atoll(e) : (uint64_t)(1u << 20); }();   // (0 in tests: every size)
         if (R >= par_min && R > 0 && n_tags <= 4096) {
+            par_numbering = true;
             // the same numbering in parallel: chunks of records count their tags, a combination's id is the order of first appearance of
             // its tag (smallest first record), a record's position the records of its combination in earlier chunks plus those before
             // it in its own
@@ -1153,6 +1156,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
             // the exchange between the walk's workgroups: granule sweep for few combinations, reduction for many (CL_CHAIN_WALK_REDUCE=0/1 pins it: A/B)
             static const char* reduce_env = getenv("CL_CHAIN_WALK_REDUCE");
             const bool reduce = walk_fold > 1 || (reduce_env ? reduce_env[0] == '1' : combos.size() > kChainWalkSweepCombos);
+            walk_reduce = reduce && combos.size() > 1;
             if (reduce && combos.size() > 1) {
                 CH(d_xred.alloc(ctx, 2 * M));
                 if (hipMemsetAsync(d_xred.p, 0, 2 * M * sizeof(uint32_t), ctx->stream) != hipSuccess) { cleanup(); cl_set_error(ctx, "hipMemsetAsync failed"); return CL_ERR_HIP; }
@@ -1666,6 +1670,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
                 if (m != peers.me) he = cl_peer_store_word_op(ctx->stream, peers.peer_flags[m] + kPeerDoneAt + peers.me, share_epoch);
         }
         if (use_far && he == hipSuccess) he = hipStreamSynchronize(seal_stream);
+        if (use_far) far_ran = far_bb ? "bb" : "sweep";   // (the mode the DP ended in: the automatic choice may leave the branch-and-bound at a checkpoint)
         // (the walk path's events are the context's ring events: nothing to destroy)
         ev_far.assign(ev_far.size(), nullptr);
     } else if (group_path) {
@@ -1711,6 +1716,10 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
         fprintf(stderr, "[chain_dp_batch]   device memory held by the context: %.1f MB (%s queries, far pass %s: %u padded records in %u levels, %u + %u tags, walk %s)\n", ctx->dev_live_bytes / 1048576.0,
                 factored ? "factored" : "dense", use_far ? "on" : "off", use_far ? F.r_pad : 0u, use_far ? F.n_levels : 0u, n_tag[0], n_tag[1],
                 !use_walk ? "off" : use_walk2 ? "2" : walk_fold > 1 ? "fold" : "1");
+        // which way the DP went where the number of combinations decides it (tests/test_gpu_combo_sweep.py reads this line)
+        fprintf(stderr, "[chain_dp_batch]   path: %s, exchange %s, fold %u, helpers %u, numbering %s, arrays %s, far %s\n", use_walk ? "walk" : group_path ? "groups" : "per-block",
+                !use_walk || combos.size() < 2 ? "none" : use_walk2 ? (walk_reduce ? "walk2+reduce" : "walk2") : walk_reduce ? "reduce" : "granules", use_walk ? std::max<uint32_t>(walk_fold, 1u) : 0u,
+                use_walk2 ? walk2_help : 0u, par_numbering ? "parallel" : "serial", d_pack.p ? "packed" : "separate", far_ran);
     }
     if (he == hipSuccess && ctx->peers.n > 1) {
         // inside a merge group the serial stream waits for the other members' arrival words: a member that has failed would leave this
@@ -1789,6 +1798,7 @@ static int chain_dp_batch_impl(cl_context* ctx, const std::vector<ChainSub>& sub
     constexpr size_t kLazyAccBytes = 1536ull << 20;
     static const char* lazy_env = getenv("CL_CHAIN_LAZY_ACC");
     const bool lazy_acc = !d_pack.p && (lazy_env ? lazy_env[0] == '1' : combos.size() * (size_t)M * 7 * sizeof(int) > kLazyAccBytes);
+    if (timing) fprintf(stderr, "[chain_dp_batch]   traceback rows %s\n", lazy_acc ? "on demand" : "downloaded");
     std::vector<int> row_host;
     uint32_t row_s = kNone;
     int* row_pin = nullptr;

@@ -450,3 +450,157 @@ def sweep_result_diff(res, z, prefix, check_score, check_choice):
         if not np.array_equal(res.score[m], z[prefix + "score"][m]):
             return "score differs at problem %d" % int(np.flatnonzero(m)[np.argmax(res.score[m] != z[prefix + "score"][m])])
     return None
+
+
+# the chaining DP across the number of chain combinations ---------------------------------------------------------------
+# (tests/test_combo_sweep.py, tests/test_gpu_combo_sweep.py, tests/golden/make_combo_sweep.py)
+# paths of graph 1 x paths of graph 2 on both sides of every count at which cl_chain_api.cpp changes its device path: 1 | 2 (the one-combination
+# specialisations), 8 | 9 (chain_walk2), 16 | 17 (granules | atomic maximum + arrival count), 256 | 257, 512 | 513, 768 | 770 (one, two, three combinations
+# per walk workgroup, then the group-by-group path), 4 096 | 4 160 tags (parallel | serial numbering), 65 535 | 65 536 (a launch dimension's limit)
+COMBO_PATHS = ((1, 1), (1, 2), (2, 2), (2, 4), (3, 3), (4, 4), (1, 17), (2, 9), (16, 16), (1, 257), (16, 32), (19, 27), (24, 32), (22, 35), (32, 33),
+               (64, 64), (64, 65), (255, 257), (256, 256), (256, 257))
+COMBO_MULTI_MAX = 1056        # the multi-block size up to here
+COMBO_TINY_MIN = 65535        # from here on: a dozen to a few dozen pairs on ancestors of about 150 bases
+COMBO_ORACLE_LIVE_S = 2.0     # cases whose oracle run takes longer are compared with tests/golden/chain_combo_sweep.npz
+
+
+class ComboCase:
+    """one input of the sweep: name, paths per side, size class ('small': at most one macro-block of kChainMacro = 1 024 pairs; 'multi': at least five, so
+    that the far pass runs; 'tiny'), the number of chain combinations it must have, and the generator's arguments"""
+
+    def __init__(self, p1, p2, size, length, pairs, seed, scale, alt_p=0.004):
+        self.p1, self.p2, self.size, self.length, self.pairs, self.seed, self.scale, self.alt_p = p1, p2, size, length, pairs, seed, scale, alt_p
+        self.combos = p1 * p2
+        self.name = "%dx%d_%s" % (p1, p2, size)
+
+    def __repr__(self):
+        return self.name
+
+
+def combo_cases():
+    out = []
+    for k, (p1, p2) in enumerate(COMBO_PATHS):
+        scale = CHAIN_SCALES[k % 3]
+        if p1 * p2 >= COMBO_TINY_MIN:
+            out.append(ComboCase(p1, p2, "tiny", 150, 24, 5000 + k, scale))
+            continue
+        out.append(ComboCase(p1, p2, "small", 1500, 300, 5000 + k, scale))
+        if p1 * p2 <= COMBO_MULTI_MAX:
+            out.append(ComboCase(p1, p2, "multi", 30000, 5200, 5100 + k, CHAIN_SCALES[(k + 1) % 3]))
+    # graphs whose paths share no node: a match pair then lies in ONE combination and has its predecessors there alone, so that every combination decides DP
+    # values of its own (over the bubble graphs above nearly every node lies on nearly every path and any one combination can be lost without a trace)
+    out.append(ComboCase(4, 4, "disjoint", 500, 900, 5200, 1.0))
+    out.append(ComboCase(1, 17, "disjoint", 500, 900, 5201, 0.05))
+    out.append(ComboCase(16, 16, "disjoint", 600, 5000, 5202, 1.0))      # 256 workgroups of the walk, five macro-blocks
+    return out
+
+
+def combo_case(name):
+    return next(c for c in combo_cases() if c.name == name)
+
+
+_combo_inputs = {}
+
+
+def combo_input(case):
+    """(graph 1, graph 2, match sets, scale) of a ComboCase, host-only and seeded: two bubble graphs over one tandem-repeat ancestor (few alternative nodes,
+    no skipped positions, so that nearly every node lies on nearly every path and every pair of paths shares a match pair), sentinels (5, 6) and (7, 8), the
+    oracle's match sets at a small max_count, thinned to the case's number of pairs"""
+    if case.name not in _combo_inputs:
+        from oracle import pyoracle as po
+        rng = np.random.default_rng(case.seed)
+        unit = rng.integers(0, 4, int(rng.integers(23, 48))).astype(np.uint8)
+        anc = np.tile(unit, case.length // len(unit) + 1)[:case.length].copy()
+        mut = rng.random(case.length) < 0.04
+        anc[mut] = rng.integers(0, 4, int(mut.sum()))
+        if case.size == "disjoint":
+            g1 = disjoint_paths_graph(anc, case.p1, case.seed, (5, 6))
+            g2 = disjoint_paths_graph(anc, case.p2, case.seed + 50000, (7, 8))
+            ms = po.budget_subset(po.oracle_find_matches(g1, g2, max_count=40), case.pairs, seed=case.seed)
+        else:
+            g1 = synth.bubble_graph(anc, case.p1, seed=case.seed, alt_p=case.alt_p, skip_p=0.0, sentinels=(5, 6))
+            g2 = synth.bubble_graph(anc, case.p2, seed=case.seed + 50000, alt_p=case.alt_p, skip_p=0.0, sentinels=(7, 8))
+            ms = po.budget_subset(po.oracle_find_matches(g1, g2, max_count=6), case.pairs, seed=case.seed)
+        _combo_inputs[case.name] = (g1, g2, ms, case.scale)
+    return _combo_inputs[case.name]
+
+
+def disjoint_paths_graph(ancestor, n_paths, seed, sentinels):
+    """capi.BaseGraph of n_paths chains between one source and one sink that share no node: each a copy of the ancestor with substitutions of its own (5 %)"""
+    rng = np.random.default_rng(seed)
+    n = len(ancestor)
+    m = n * n_paths
+    label = np.tile(np.asarray(ancestor, np.uint8), n_paths)
+    sub = rng.random(m) < 0.05
+    label[sub] = (label[sub] + rng.integers(1, 4, int(sub.sum()))) % 4
+    src, snk = m, m + 1
+    nxt = [[v + 1] if (v + 1) % n else [snk] for v in range(m)] + [[p * n for p in range(n_paths)], []]
+    prv = [[v - 1] if v % n else [src] for v in range(m)] + [[], [p * n + n - 1 for p in range(n_paths)]]
+    def csr(lists):
+        return np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.uint64), np.array([v for x in lists for v in x], np.uint32)
+    no, ni = csr(nxt)
+    po_, pi = csr(prv)
+    return capi.BaseGraph(np.concatenate([label, np.array(sentinels, np.uint8)]), no, ni, po_, pi, (np.arange(n_paths + 1) * n).astype(np.uint64),
+                          np.arange(m, dtype=np.uint32), src, snk)
+
+
+def _paths_on(g):
+    """[node][path] -> does the path visit the node"""
+    on = np.zeros((len(g.label), len(g.path_off) - 1), bool)
+    for p in range(len(g.path_off) - 1):
+        on[g.path_nodes[int(g.path_off[p]):int(g.path_off[p + 1])], p] = True
+    return on
+
+
+def count_combinations(g1, g2, ms):
+    """the number of chain combinations of the affine DP, from the inputs alone: pairs (path of graph 1, path of graph 2) such that some match pair ends on a
+    node of the one in graph 1 and on a node of the other in graph 2 (a pair leaves one record in every combination of the paths its two end nodes lie on)"""
+    on = (_paths_on(g1), _paths_on(g2))
+    covered = np.zeros((on[0].shape[1], on[1].shape[1]), bool)
+    for s in range(ms.n_sets):
+        rows = []
+        for side, o in (("1", on[0]), ("2", on[1])):
+            so, wo, nodes = getattr(ms, "set_off" + side), getattr(ms, "walk_off" + side), getattr(ms, "nodes" + side)
+            ends = [int(nodes[int(wo[w + 1]) - 1]) for w in range(int(so[s]), int(so[s + 1]))]
+            rows.append(o[ends].any(axis=0) if ends else np.zeros(o.shape[1], bool))
+        covered |= np.outer(rows[0], rows[1])
+    return int(covered.sum())
+
+
+def count_records(g1, g2, ms):
+    """the records of the affine DP, from the inputs alone: every match pair leaves one in each combination of a path its end node lies on in graph 1 with one in graph 2"""
+    n_on = [_paths_on(g).sum(axis=1) for g in (g1, g2)]
+    total = 0
+    for s in range(ms.n_sets):
+        per_side = []
+        for side, n in (("1", n_on[0]), ("2", n_on[1])):
+            so, wo, nodes = getattr(ms, "set_off" + side), getattr(ms, "walk_off" + side), getattr(ms, "nodes" + side)
+            per_side.append(sum(int(n[int(nodes[int(wo[w + 1]) - 1])]) for w in range(int(so[s]), int(so[s + 1]))))
+        total += per_side[0] * per_side[1]
+    return total
+
+
+def combo_input_digest(g1, g2, ms, scale):
+    h = hashlib.sha256()
+    for g in (g1, g2):
+        for k in ("label", "next_off", "next_idx", "prev_off", "prev_idx", "path_off", "path_nodes"):
+            h.update(np.ascontiguousarray(getattr(g, k)).tobytes())
+        h.update(np.array([g.src_id, g.snk_id], np.uint64).tobytes())
+    h.update(match_sets_digest(ms).encode())
+    h.update(np.array([scale], np.float64).tobytes())
+    return h.hexdigest()
+
+
+def combo_oracle_is_live(case):
+    """can a test afford the oracle on this case (about 2 s at most)?  Its cost grows with pairs x combinations and faster than linearly in the pairs: measured
+    0.9 s at 300 pairs x 257 combinations and 2.0 s at 300 x 512; 1.6 s at 5 200 x 16 and 53 s at 5 200 x 256; 4 - 8 s on the tiny cases.  The others are compared
+    with tests/golden/chain_combo_sweep.npz"""
+    if case.size == "disjoint":      # (one record per pair: 0.1 s at 5 000 pairs x 256 combinations)
+        return True
+    return case.combos <= (257 if case.size == "small" else 18 if case.size == "multi" else 0)
+
+
+def combo_ref_can_run(case):
+    """the compiled reference's sparse_affine_chain_dp did not finish within two minutes at 1 x 257 paths and 300 pairs (the oracle: 0.9 s): it is run on the
+    cases with fewer than 256 paths on either side"""
+    return max(case.p1, case.p2) < 256
