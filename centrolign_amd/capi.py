@@ -458,6 +458,71 @@ def induced_pairwise_stats(graph, pairs, ctx):
     return out
 
 
+PAIR_WINDOW_FIELDS = ("eq", "x", "ins", "del")   # cl_pair_window, in the struct's order
+GAP_EVENT_DTYPE = np.dtype([("pos1", "<u8"), ("pos2", "<u8"), ("len", "<u8"), ("op", "<u4"), ("reserved", "<u4")])   # cl_gap_event; op 0: D, 1: I
+
+
+def _take_array(p, n, dtype, shape):
+    """a copy of n elements of `dtype` at the malloc'ed pointer p, which is released"""
+    try:
+        nbytes = int(n) * np.dtype(dtype).itemsize
+        raw = (C.c_char * nbytes).from_address(p.value) if nbytes else b""
+        return np.frombuffer(raw, dtype).reshape(shape).copy()
+    finally:
+        _libc_free(p)
+
+
+def induced_pairwise_profile(graph, path1, path2, window):
+    """cl_induced_pairwise_profile (host only): the columns of induced_pairwise_cigar(graph, path1, path2) per window of `window` bases of path 1;
+    a uint64 array [n_win, 4] with PAIR_WINDOW_FIELDS as columns"""
+    lib = load_library()
+    g, p, n = graph.as_c(), C.c_void_p(), C.c_uint64(0)
+    lib.cl_induced_pairwise_profile.restype = C.c_int
+    lib.cl_induced_pairwise_profile.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    rc = lib.cl_induced_pairwise_profile(C.byref(g), int(path1), int(path2), int(window), C.byref(p), C.byref(n))
+    if rc != 0:
+        raise ClError(rc, "cl_induced_pairwise_profile")
+    return _take_array(p, 4 * int(n.value), np.uint64, (-1, 4))
+
+
+def induced_gap_events(graph, path1, path2, min_len):
+    """cl_induced_gap_events (host only): the I and D runs of at least min_len bases of induced_pairwise_cigar(graph, path1, path2), in CIGAR order;
+    an array of GAP_EVENT_DTYPE (pos1, pos2: the place of the run's first column; op 0: D, 1: I)"""
+    lib = load_library()
+    g, p, n = graph.as_c(), C.c_void_p(), C.c_uint64(0)
+    lib.cl_induced_gap_events.restype = C.c_int
+    lib.cl_induced_gap_events.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    rc = lib.cl_induced_gap_events(C.byref(g), int(path1), int(path2), int(min_len), C.byref(p), C.byref(n))
+    if rc != 0:
+        raise ClError(rc, "cl_induced_gap_events")
+    return _take_array(p, int(n.value), GAP_EVENT_DTYPE, (-1,))
+
+
+def _induced_positions_batch(name, graph, pairs, arg, ctx, dtype, per_element, shape):
+    lib = load_library()
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+    n = len(pairs)
+    g, p, off = graph.as_c(), C.c_void_p(), np.zeros(n + 1, np.uint64)
+    fn = getattr(lib, name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]
+    ctx._check(fn(ctx.handle, C.byref(g), pairs.ctypes.data, n, int(arg), C.byref(p), off.ctypes.data))
+    flat = _take_array(p, int(off[-1]) * per_element, dtype, shape)
+    return [flat[int(off[k]):int(off[k + 1])] for k in range(n)]
+
+
+def induced_pairwise_profiles(graph, pairs, window, ctx):
+    """cl_induced_pairwise_profiles: induced_pairwise_profile of every (path1, path2) row of `pairs` in one device pass on Context ctx; a list with
+    one uint64 array [n_win, 4] per pair.  Raises ClError with the host function's code for the first failing pair."""
+    return _induced_positions_batch("cl_induced_pairwise_profiles", graph, pairs, window, ctx, np.uint64, 4, (-1, 4))
+
+
+def induced_gap_events_batch(graph, pairs, min_len, ctx):
+    """cl_induced_gap_events_batch: induced_gap_events of every (path1, path2) row of `pairs` in one device pass on Context ctx; a list with one
+    array of GAP_EVENT_DTYPE per pair.  Raises ClError with the host function's code for the first failing pair."""
+    return _induced_positions_batch("cl_induced_gap_events_batch", graph, pairs, min_len, ctx, GAP_EVENT_DTYPE, 1, (-1,))
+
+
 def alignment_distances(stats, n):
     """cl_alignment_distances (host only): the [n, n] float64 matrix d = 1 - 2 eq / (2 eq + 2 x + ins + del) of the n * (n - 1) / 2 rows of `stats`
     (induced_pairwise_stats of the pairs (a, b), a < b, a outer)"""
@@ -1235,7 +1300,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 16    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 17    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1451,6 +1516,7 @@ EXPORTED_SYMBOLS = [
     "cl_config_msa_params",
     "cl_kmer_distances_compute", "cl_kmer_distances_free", "cl_neighbor_joining_newick", "cl_infer_guide_tree",
     "cl_induced_pairwise_stat", "cl_induced_pairwise_stats", "cl_alignment_distances", "cl_refine_guide_tree",
+    "cl_induced_pairwise_profile", "cl_induced_pairwise_profiles", "cl_induced_gap_events", "cl_induced_gap_events_batch",
 ]
 
 

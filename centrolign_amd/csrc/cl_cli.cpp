@@ -8,9 +8,13 @@
 //     writes it;
 //   - --refine-tree N rebuilds the guide tree from the distances of an alignment made under it (cl_refine_guide_tree), up to N times, before the
 //     alignment proper; --pair-stats and --dist-out write the pairwise statistics and distances the final alignment implies;
+//   - --pair-profile (with --window) and --pair-events (with --min-event) write, for every pair of sequences, the induced alignment's columns per
+//     window of the first sequence and its long insertions and deletions with their positions (cl_induced_pairwise_profiles,
+//     cl_induced_gap_events_batch on the printed graph); not with -c, whose final graph has cycles;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -147,6 +151,89 @@ bool write_distances(const std::string& stats_file, const std::vector<std::strin
     return true;
 }
 
+// a whole number >= 1 (--window, --min-event)
+bool parse_positive(const std::string& text, uint64_t& out) {
+    if (text.empty() || text.size() > 18) return false;
+    for (char c : text) if (c < '0' || c > '9') return false;
+    out = strtoull(text.c_str(), nullptr, 10);
+    return out >= 1;
+}
+
+// --pair-profile / --pair-events: the GFA text the run printed is read back (cl_read_gfa, as cl_refine_guide_tree does) and every pair (p, q), p < q,
+// of its paths goes through the batch entry points; names as --pair-stats writes them
+bool write_pair_positions(cl_context* ctx, const char* gfa, uint64_t gfa_len, const std::string& profile_file, uint64_t window, const std::string& events_file,
+                          uint64_t min_event, std::string& err) {
+    cl_owned_base_graph* owned = nullptr;
+    char** path_names = nullptr;
+    uint64_t n_paths = 0;
+    if (cl_read_gfa(gfa, gfa_len, 1, &owned, &path_names, &n_paths)) { err = "cannot read back the alignment graph"; return false; }
+    struct FreeGraph { cl_owned_base_graph* g; ~FreeGraph() { cl_owned_base_graph_free(g); } } free_graph{owned};
+    std::vector<std::string> names;
+    for (uint64_t p = 0; p < n_paths; ++p) {
+        names.emplace_back(path_names[p]);
+        for (char& c : names.back()) if (c == '/') c = '_';
+        free(path_names[p]);
+    }
+    free(path_names);
+    cl_base_graph g;
+    cl_owned_base_graph_view(owned, &g);
+    std::vector<uint64_t> pairs;
+    for (uint64_t p = 0; p < n_paths; ++p)
+        for (uint64_t q = p + 1; q < n_paths; ++q) { pairs.push_back(p); pairs.push_back(q); }
+    const uint64_t n_pairs = pairs.size() / 2;
+    std::vector<uint64_t> off(n_pairs + 1);
+    auto lib_failure = [&](const char* what) {
+        const char* e = cl_last_error(ctx);
+        err = std::string(what) + ": " + (e && *e ? e : "failed");
+        return false;
+    };
+    auto write_file = [&](const std::string& name, const std::string& text) {
+        std::ofstream out(name, std::ios::binary);
+        if (out) out.write(text.data(), (std::streamsize)text.size());
+        out.close();
+        if (!out) err = "could not write to " + name;
+        return (bool)out;
+    };
+    if (!profile_file.empty()) {
+        cl_pair_window* win = nullptr;
+        if (cl_induced_pairwise_profiles(ctx, &g, pairs.data(), n_pairs, window, &win, off.data())) return lib_failure("pairwise profiles of the alignment graph");
+        std::string tsv = "sample1\tsample2\twindow_start\twindow_end\tmatches\tmismatches\tinsertions\tdeletions\n";
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const uint64_t n1 = g.path_off[pairs[2 * k] + 1] - g.path_off[pairs[2 * k]];
+            const std::string lead = names[pairs[2 * k]] + "\t" + names[pairs[2 * k + 1]];
+            for (uint64_t w = 0; w < off[k + 1] - off[k]; ++w) {
+                const cl_pair_window& c = win[off[k] + w];
+                char num[160];
+                snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)std::min(w * window, n1),
+                         (unsigned long long)std::min((w + 1) * window, n1), (unsigned long long)c.eq, (unsigned long long)c.x, (unsigned long long)c.ins,
+                         (unsigned long long)c.del);
+                tsv += lead;
+                tsv += num;
+            }
+        }
+        free(win);
+        if (!write_file(profile_file, tsv)) return false;
+    }
+    if (!events_file.empty()) {
+        cl_gap_event* ev = nullptr;
+        if (cl_induced_gap_events_batch(ctx, &g, pairs.data(), n_pairs, min_event, &ev, off.data())) return lib_failure("gap events of the alignment graph");
+        std::string tsv = "sample1\tsample2\ttype\tpos1\tpos2\tlength\n";
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const std::string lead = names[pairs[2 * k]] + "\t" + names[pairs[2 * k + 1]];
+            for (uint64_t i = off[k]; i < off[k + 1]; ++i) {
+                char num[128];
+                snprintf(num, sizeof(num), "\t%c\t%llu\t%llu\t%llu\n", ev[i].op ? 'I' : 'D', (unsigned long long)ev[i].pos1, (unsigned long long)ev[i].pos2,
+                         (unsigned long long)ev[i].len);
+                tsv += lead;
+                tsv += num;
+            }
+        }
+        free(ev);
+        if (!write_file(events_file, tsv)) return false;
+    }
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -181,10 +268,15 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --tree-out FILE             With --infer-tree or --refine-tree, write the Newick tree the alignment used to FILE\n");
     fprintf(o, " --pair-stats FILE           Write matches, mismatches, gap bases, runs and distance of every pair of sequences to FILE (which must not exist yet)\n");
     fprintf(o, " --dist-out FILE             Write the matrix of pairwise alignment distances, in FASTA order, to FILE\n");
+    fprintf(o, " --pair-profile FILE         Write matches, mismatches and gap bases of every pair of sequences per window of the first one to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --window INT                With --pair-profile, the window in bases of the first sequence [1000]\n");
+    fprintf(o, " --pair-events FILE          Write every insertion and deletion of at least --min-event bases between two sequences, with its positions, to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --min-event INT             With --pair-events, the least length of an insertion or deletion that is written [50]\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
-    fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats and --dist-out are added; -v gates this tool's own\n");
+    fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats, --dist-out, --pair-profile, --window,\n");
+    fprintf(o, "--pair-events and --min-event are added; -v gates this tool's own\n");
     fprintf(o, "progress lines. See README.md.\n");
 }
 
@@ -207,12 +299,13 @@ int run(int argc, char** argv) {
     cl_config* cfg = own.cfg;
 
     std::string config_name;
-    std::string tree_out, pair_stats, dist_out, refine_arg;
-    bool force_gfa_output = false, generate_config = false, infer_tree = false;
+    std::string tree_out, pair_stats, dist_out, refine_arg, pair_profile, pair_events, window_arg, min_event_arg;
+    bool force_gfa_output = false, generate_config = false, infer_tree = false, have_window = false, have_min_event = false;
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
-           OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009 };
+           OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009,
+           OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -240,6 +333,10 @@ int run(int argc, char** argv) {
         {"pair-stats", required_argument, nullptr, OPT_PAIR_STATS},
         {"dist-out", required_argument, nullptr, OPT_DIST_OUT},
         {"refine-tree", required_argument, nullptr, OPT_REFINE_TREE},
+        {"pair-profile", required_argument, nullptr, OPT_PAIR_PROFILE},
+        {"window", required_argument, nullptr, OPT_WINDOW},
+        {"pair-events", required_argument, nullptr, OPT_PAIR_EVENTS},
+        {"min-event", required_argument, nullptr, OPT_MIN_EVENT},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -277,6 +374,10 @@ int run(int argc, char** argv) {
         case OPT_PAIR_STATS: pair_stats = optarg; break;
         case OPT_DIST_OUT: dist_out = optarg; break;
         case OPT_REFINE_TREE: refine_arg = optarg; break;
+        case OPT_PAIR_PROFILE: pair_profile = optarg; break;
+        case OPT_WINDOW: window_arg = optarg; have_window = true; break;
+        case OPT_PAIR_EVENTS: pair_events = optarg; break;
+        case OPT_MIN_EVENT: min_event_arg = optarg; have_min_event = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -327,6 +428,19 @@ int run(int argc, char** argv) {
         if (config_value(cfg, "restart") == "true") return fail("--refine-tree cannot be combined with a restart (-R)");
     }
     if (!pair_stats.empty() && std::ifstream(pair_stats).good()) return fail("Pair statistics file already exists: " + pair_stats);
+    // --pair-profile / --pair-events, also checked before anything is read or opened
+    uint64_t window = 1000, min_event = 50;
+    if (have_window && pair_profile.empty()) return fail("--window needs --pair-profile");
+    if (have_min_event && pair_events.empty()) return fail("--min-event needs --pair-events");
+    if (have_window && !parse_positive(window_arg, window)) return fail("--window expects a whole number of bases, at least 1, got '" + window_arg + "'");
+    if (have_min_event && !parse_positive(min_event_arg, min_event))
+        return fail("--min-event expects a whole number of bases, at least 1, got '" + min_event_arg + "'");
+    if (!pair_profile.empty() && std::ifstream(pair_profile).good()) return fail("Pair profile file already exists: " + pair_profile);
+    if (!pair_events.empty() && std::ifstream(pair_events).good()) return fail("Pair events file already exists: " + pair_events);
+    if (!pair_profile.empty() && pair_profile == pair_events) return fail("--pair-profile and --pair-events name the same file");
+    const bool pair_positions = !pair_profile.empty() || !pair_events.empty();
+    if (pair_positions && config_value(cfg, "cyclize_tandem_duplications") == "true")
+        return fail("--pair-profile and --pair-events cannot be combined with -c: the final graph then has cycles");
     // --dist-out alone passes the rows through a file of its own next to FILE, which must not be anybody else's
     const std::string dist_tmp = !dist_out.empty() && pair_stats.empty() ? dist_out + ".pair-stats.tmp" : std::string();
     if (!dist_tmp.empty() && std::ifstream(dist_tmp).good()) return fail("--dist-out would overwrite " + dist_tmp + ": remove it or give --pair-stats");
@@ -359,6 +473,8 @@ int run(int argc, char** argv) {
     if (n_sequences < 2)
         return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains " + std::to_string(n_sequences) +
                     " sequence(s), cannot form an alignment");
+    if (pair_positions && n_sequences == 2 && !force_gfa_output)
+        return fail("--pair-profile and --pair-events need --force-gfa-output for two sequences: they read the graph that is printed");
     if (!dist_out.empty()) {   // the rows name sequences as -A names its files: two names that differ only in '/' and '_' could not be told apart
         std::vector<std::string> flat = sequence_names;
         for (std::string& nm : flat) for (char& c : nm) if (c == '/') c = '_';
@@ -446,8 +562,11 @@ int run(int argc, char** argv) {
         return fail(e && *e ? e : lib_error());
     }
     const bool written = fwrite(text, 1, len, stdout) == len && fflush(stdout) == 0;
+    std::string positions_err;
+    const bool positions_ok = !written || !pair_positions || write_pair_positions(own.ctx, text, len, pair_profile, window, pair_events, min_event, positions_err);
     free(text);
     if (!written) return fail("could not write the alignment to standard output");
+    if (!positions_ok) return fail(positions_err);
     if (!dist_out.empty()) {
         std::string err;
         const bool ok = write_distances(stats_file, sequence_names, dist_out, err);

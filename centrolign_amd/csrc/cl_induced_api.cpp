@@ -3,6 +3,10 @@
 //                               host restatement cl_induced_pairwise_cigar (cl_io_api.cpp) is what it is checked against
 //   cl_induced_pairwise_stats   the same alignments as counters (bases and runs per op) in one device pass of their own kernel, no text; it shares
 //                               the position tables and the chunking with the call above (induced_batch); host restatement: cl_induced_pairwise_stat
+//   cl_induced_pairwise_profiles, cl_induced_gap_events_batch
+//                               the same alignments by position: per window of path 1 the columns of each letter, and the I / D runs of a least
+//                               length with their places; one kernel each over the same frame, no text; host restatements:
+//                               cl_induced_pairwise_profile, cl_induced_gap_events
 //   cl_induced_cyclic_maf       output_maf(induced_cyclic_pairwise_alignment(...)) (src/alignment.cpp:229-904), the output after cyclisation.
 //                               Host code: its core is a Hunt-Szymanski LCS, a dependent chain of binary searches over a threshold row
 //                               (DESIGN.md §9); the caller runs pairs in parallel, as the reference does (core.cpp:554-591).
@@ -27,8 +31,10 @@ char* c_string(const std::string& s, uint64_t* len_out) {
 
 constexpr uint64_t kGap = ~(uint64_t)0;
 // device working memory of one chunk of cl_induced_pairwise_cigars / _stats: the position tables of the chunk's first paths (4 bytes per node each);
-// the text of a write pass is bounded the same way (a single pair's CIGAR may exceed it alone).  A chunk also holds at most kChunkPairs pairs.
+// the text of a write pass is bounded the same way (a single pair's CIGAR may exceed it alone), and so are the windows of a profile pass and the
+// events of an event write pass.  A chunk also holds at most kChunkPairs pairs.
 constexpr uint64_t kChunkTableBytes = 256ull << 20, kChunkTextBytes = 256ull << 20, kChunkPairs = 2048;
+constexpr uint64_t kChunkWindows = (256ull << 20) / sizeof(cl_pair_window), kChunkEvents = (256ull << 20) / sizeof(cl_gap_event);
 
 // ---------------------------------------------------------------- the cyclic MAF -------------------------------------------------------------
 using Pair = std::pair<uint64_t, uint64_t>;   // (index on path 1, index on path 2), kGap: none
@@ -378,7 +384,7 @@ struct InducedChunk {
     const uint32_t* d_tables;
 };
 
-// The frame of cl_induced_pairwise_cigars and cl_induced_pairwise_stats: the checks the host makes (cl_induced_pairwise_cigar's order), the
+// The frame of cl_induced_pairwise_cigars, _stats, _profiles and cl_induced_gap_events_batch: the checks the host makes (cl_induced_pairwise_cigar's order), the
 // graph on the device, the pairs ordered by first path and cut into chunks, each chunk's position tables (scatter + check), then pass(chunk)
 // for the entry point's own kernels and copies, and at the end the code of the first failing pair.
 template <class Pass>
@@ -557,6 +563,107 @@ int cl_induced_pairwise_stats(cl_context* ctx, const cl_base_graph* g, const uin
         for (size_t j = 0; j < stats.size(); ++j) out[c.job_pair[j]] = stats[j];
         return CL_OK;
     });
+}
+
+int cl_induced_pairwise_profiles(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, uint64_t window, cl_pair_window** out,
+                                 uint64_t* offsets_out) {
+    cl_bind_device(ctx);
+    if (!ctx || !g || (n_pairs && !pairs) || !out || !offsets_out) return CL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (window == 0) { cl_set_error(ctx, "the window of a pairwise profile must be at least 1"); return CL_ERR_INVALID_ARGUMENT; }
+    // a pair's windows follow from the length of its first path: the result's layout is known before the device runs
+    auto n_windows = [&](uint64_t n1) { return std::max<uint64_t>(1, n1 / window + (n1 % window != 0)); };
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        offsets_out[k] = total;
+        const uint64_t a = pairs[2 * k];
+        if (a < g->n_paths && pairs[2 * k + 1] < g->n_paths) total += n_windows(g->path_off[a + 1] - g->path_off[a]);
+    }
+    offsets_out[n_pairs] = total;
+    cl_pair_window* win = (cl_pair_window*)malloc(std::max<uint64_t>(total, 1) * sizeof(cl_pair_window));
+    if (!win) return CL_ERR_OUT_OF_MEMORY;
+    const uint64_t width = std::min<uint64_t>(window, 1ull << 40);   // (beyond any path: one window either way; the kernel computes in int64_t)
+    std::vector<cl_pair_window> host;
+    const int rc = induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
+        std::vector<ClInducedJob>& jobs = c.jobs;
+        int rc;
+        // passes over groups of jobs whose windows fit in kChunkWindows (at least one job)
+        for (size_t w0 = 0; w0 < jobs.size();) {
+            size_t w1 = w0;
+            uint64_t n = 0;
+            while (w1 < jobs.size() && (w1 == w0 || n + n_windows(jobs[w1].n1) <= kChunkWindows)) {
+                jobs[w1].text_off = n;
+                jobs[w1].text_cap = n_windows(jobs[w1].n1);
+                n += jobs[w1].text_cap;
+                ++w1;
+            }
+            DevBuf<ClInducedJob> d_jobs;
+            DevBuf<cl_pair_window> d_win;
+            std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
+            if (host.size() < n) host.resize(n);
+            if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_win.alloc(ctx, n))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(d_win.p, 0, n * sizeof(cl_pair_window), ctx->stream));
+            HIP_TRY(ctx, cl_launch_induced_profile(d_jobs.p, (uint32_t)sub.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, width, d_win.p, ctx->stream));
+            HIP_TRY(ctx, cl_copy_sync(ctx, host.data(), d_win.p, n * sizeof(cl_pair_window), hipMemcpyDeviceToHost));
+            for (size_t j = w0; j < w1; ++j) memcpy(win + offsets_out[c.job_pair[j]], host.data() + jobs[j].text_off, jobs[j].text_cap * sizeof(cl_pair_window));
+            w0 = w1;
+        }
+        return CL_OK;
+    });
+    if (rc) { free(win); return rc; }
+    *out = win;
+    return CL_OK;
+}
+
+int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, uint64_t min_len, cl_gap_event** out,
+                                uint64_t* offsets_out) {
+    cl_bind_device(ctx);
+    if (!ctx || !g || (n_pairs && !pairs) || !out || !offsets_out) return CL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (min_len == 0) { cl_set_error(ctx, "the least length of a gap event must be at least 1"); return CL_ERR_INVALID_ARGUMENT; }
+    std::vector<std::vector<cl_gap_event>> events(n_pairs);
+    std::vector<cl_gap_event> host;
+    int rc = induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
+        std::vector<ClInducedJob>& jobs = c.jobs;
+        int rc;
+        DevBuf<ClInducedJob> d_jobs;
+        DevBuf<int64_t> d_cnt;
+        std::vector<int64_t> cnt(jobs.size());
+        if ((rc = d_jobs.upload(ctx, jobs)) || (rc = d_cnt.alloc(ctx, jobs.size()))) return rc;
+        HIP_TRY(ctx, cl_launch_induced_events(false, d_jobs.p, (uint32_t)jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, min_len, d_cnt.p, nullptr, ctx->stream));
+        HIP_TRY(ctx, cl_copy_sync(ctx, cnt.data(), d_cnt.p, cnt.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        // write passes over groups of jobs whose events fit in kChunkEvents (at least one job)
+        for (size_t w0 = 0; w0 < jobs.size();) {
+            size_t w1 = w0;
+            uint64_t n = 0;
+            while (w1 < jobs.size() && (w1 == w0 || n + (uint64_t)cnt[w1] <= kChunkEvents)) {
+                jobs[w1].text_off = n;
+                jobs[w1].text_cap = (uint64_t)cnt[w1];
+                n += (uint64_t)cnt[w1];
+                ++w1;
+            }
+            if (n) {
+                DevBuf<cl_gap_event> d_ev;
+                std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
+                if (host.size() < n) host.resize(n);
+                if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_ev.alloc(ctx, n))) return rc;
+                HIP_TRY(ctx, cl_launch_induced_events(true, d_jobs.p, (uint32_t)sub.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, min_len, nullptr, d_ev.p, ctx->stream));
+                HIP_TRY(ctx, cl_copy_sync(ctx, host.data(), d_ev.p, n * sizeof(cl_gap_event), hipMemcpyDeviceToHost));
+                for (size_t j = w0; j < w1; ++j) events[c.job_pair[j]].assign(host.begin() + jobs[j].text_off, host.begin() + jobs[j].text_off + jobs[j].text_cap);
+            }
+            w0 = w1;
+        }
+        return CL_OK;
+    });
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < n_pairs; ++k) { offsets_out[k] = total; total += events[k].size(); }
+    offsets_out[n_pairs] = total;
+    cl_gap_event* ev = (cl_gap_event*)malloc(std::max<uint64_t>(total, 1) * sizeof(cl_gap_event));
+    if (!ev) return CL_ERR_OUT_OF_MEMORY;
+    for (uint64_t k = 0; k < n_pairs; ++k) if (!events[k].empty()) memcpy(ev + offsets_out[k], events[k].data(), events[k].size() * sizeof(cl_gap_event));
+    *out = ev;
+    return CL_OK;
 }
 
 }  // extern "C"

@@ -370,6 +370,13 @@ hipError_t cl_launch_induced_runs(bool write, const ClInducedJob* jobs, uint32_t
 // the statistics of the same alignments (cl_induced_pairwise_stats): one pass, stats[j] for job j; text_off / text_cap are not read
 hipError_t cl_launch_induced_stats(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
                                    const uint32_t* tables, cl_pair_stats* stats, hipStream_t stream);
+// the same alignments by position.  Profile (cl_induced_pairwise_profiles): text_off / text_cap are the pair's first window in `windows` and its
+// number of windows; the bins must be zero.  Events (cl_induced_gap_events_batch): the counting pass writes n_events[j]; the write pass puts the
+// events of job j at events[text_off .. text_off + text_cap)
+hipError_t cl_launch_induced_profile(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                     const uint32_t* tables, uint64_t window, cl_pair_window* windows, hipStream_t stream);
+hipError_t cl_launch_induced_events(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
+                                    uint64_t n_nodes, const uint32_t* tables, uint64_t min_len, int64_t* n_events, cl_gap_event* events, hipStream_t stream);
 
 // subaln_kernels.hip: the -s lines of one merge (cl_subaln_api.cpp).  One side of the merge on the device: the per-node step table
 // ((path << 32) | step of the node's first occurrence, UINT64_MAX: on no path), the labels, and the path names back to back

@@ -395,4 +395,54 @@ int cl_induced_pairwise_stat(const cl_base_graph* g, uint64_t path1, uint64_t pa
     return CL_OK;
 }
 
+// the same alignment by position (header): the columns of each letter per window of path 1, i1 taken in front of the column
+int cl_induced_pairwise_profile(const cl_base_graph* g, uint64_t path1, uint64_t path2, uint64_t window, cl_pair_window** out, uint64_t* n_win_out) {
+    if (!out || !n_win_out || window == 0) return CL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    InducedAln aln;
+    const int rc = induced_pairwise_alignment(g, path1, path2, aln);
+    if (rc) return rc;
+    const uint64_t n1 = g->path_off[path1 + 1] - g->path_off[path1];
+    const uint64_t n_win = std::max<uint64_t>(1, n1 / window + (n1 % window != 0));
+    cl_pair_window* win = (cl_pair_window*)calloc(n_win, sizeof(cl_pair_window));
+    if (!win) return CL_ERR_OUT_OF_MEMORY;
+    uint64_t i1 = 0;
+    for (const auto& ap : aln) {
+        const char op = induced_op(g, path1, path2, ap);
+        cl_pair_window& w = win[std::min(i1 / window, n_win - 1)];
+        ++(op == '=' ? w.eq : op == 'X' ? w.x : op == 'I' ? w.ins : w.del);
+        i1 += op != 'I';
+    }
+    *out = win;
+    *n_win_out = n_win;
+    return CL_OK;
+}
+
+// the I and D runs of at least min_len columns, with the place of their first column
+int cl_induced_gap_events(const cl_base_graph* g, uint64_t path1, uint64_t path2, uint64_t min_len, cl_gap_event** out, uint64_t* n_out) {
+    if (!out || !n_out || min_len == 0) return CL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    InducedAln aln;
+    const int rc = induced_pairwise_alignment(g, path1, path2, aln);
+    if (rc) return rc;
+    std::vector<cl_gap_event> ev;
+    uint64_t i1 = 0, i2 = 0;
+    for (size_t i = 0; i < aln.size();) {
+        const char op = induced_op(g, path1, path2, aln[i]);
+        size_t e = i + 1;
+        while (e < aln.size() && induced_op(g, path1, path2, aln[e]) == op) ++e;
+        const uint64_t len = e - i;
+        if ((op == 'I' || op == 'D') && len >= min_len) ev.push_back(cl_gap_event{i1, i2, len, op == 'I' ? 1u : 0u, 0u});
+        if (op != 'I') i1 += len;
+        if (op != 'D') i2 += len;
+        i = e;
+    }
+    cl_gap_event* p = (cl_gap_event*)malloc(std::max<size_t>(ev.size(), 1) * sizeof(cl_gap_event));
+    if (!p) return CL_ERR_OUT_OF_MEMORY;
+    if (!ev.empty()) memcpy(p, ev.data(), ev.size() * sizeof(cl_gap_event));
+    *out = p;
+    *n_out = ev.size();
+    return CL_OK;
+}
+
 }  // extern "C"

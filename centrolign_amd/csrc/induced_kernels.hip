@@ -23,6 +23,12 @@
 // tokens are the same; scan 2's monoid becomes (bases per op, runs per op, first op, last op) of a token segment, joined with the run that spans
 // the seam counted once.  Only the whole pair's element is wanted, so a tile is reduced in order rather than scanned, in one pass: nothing is
 // stored per step and no text exists; each pair's eight counters are written once at the end.
+//
+// cl_induced_pairwise_profiles (induced_profile_kernel) and cl_induced_gap_events_batch (induced_events_kernel) want the tokens with their places:
+// i1 and i2 of the CIGAR walk in front of a token's first column.  These too follow from scan 1 alone: for matched step k the gap run starts at
+// (e_prev + 1, last + 1), its D token has length e - e_prev - 1, its I token stands at (e, last + 1) and the match at (e, s).  So neither needs a
+// positional scan.  The profile adds every token to the bins of the path-1 windows it covers (integer atomics, reduced per wave first: the result
+// does not depend on scheduling); the events kernel counts, then writes, the I and D tokens of at least min_len bases, each of which is one run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -145,6 +151,27 @@ __device__ __forceinline__ void match_tokens(const PairView& v, const MatchScan&
     const int64_t e_prev = k > 0 ? k - 1 + (x.best > 0 ? x.best : 0) : -1;
     gap_run_tokens(v, e_prev, x.last, s - x.last - 1, e - e_prev - 1, tok);
     tok((uint32_t)pair_op(v, e, s), (int64_t)1);
+}
+
+// The same tokens with their places: tok(op, cnt, i1, i2), i1 / i2 being the path-1 / path-2 index of the CIGAR walk in front of the token's first
+// column.  Every D or I token is one whole run of the CIGAR: a match stands on either side of a gap run.
+template <class F>
+__device__ __forceinline__ void gap_run_tokens_at(const PairView& v, int64_t last1, int64_t last2, int64_t g1, int64_t g2, F&& tok) {
+    if (g1 == g2 && g1 <= 4) {
+        for (int64_t n = 0; n < g1; ++n) tok(pair_op(v, last1 + n + 1, last2 + n + 1), (int64_t)1, last1 + n + 1, last2 + n + 1);
+    } else {
+        if (g2) tok((uint32_t)kOpD, g2, last1 + 1, last2 + 1);
+        if (g1) tok((uint32_t)kOpI, g1, last1 + 1 + g2, last2 + 1);
+    }
+}
+template <class F>
+__device__ __forceinline__ void match_tokens_at(const PairView& v, const MatchScan& x, int64_t s, int64_t a, F&& tok) {
+    const int64_t k = x.cnt;
+    const int64_t best = x.best > a - k ? x.best : a - k;
+    const int64_t e = k + (best > 0 ? best : 0);
+    const int64_t e_prev = k > 0 ? k - 1 + (x.best > 0 ? x.best : 0) : -1;
+    gap_run_tokens_at(v, e_prev, x.last, s - x.last - 1, e - e_prev - 1, tok);
+    tok((uint32_t)pair_op(v, e, s), (int64_t)1, e, s);
 }
 
 // the run scan element of a token sequence that follows a run of op `cur`
@@ -361,6 +388,225 @@ __global__ void __launch_bounds__(kThreads) induced_stats_kernel(const ClInduced
     stats[blockIdx.x] = out;
 }
 
+// ------------------------------------------------------------- windowed profiles --------------------------------------------------------------
+// The bins of one pair: n_win windows of `width` path-1 bases, the last one open-ended (it takes every column at or past its start: trailing
+// insertions, and path-1 indices past path 1's end, see pair_op).  A thread's tokens come in non-decreasing i1, so it keeps the counts of the
+// window it is in in registers and moves on with seek(); a count leaves the registers as one integer atomic per non-zero counter.
+struct WindowBins {
+    unsigned long long* bins;   // [n_win][4]: eq, x, ins, del (cl_pair_window)
+    int64_t width, last;        // last = n_win - 1
+    __device__ void add(int64_t w, uint32_t field, uint64_t n) const {
+        if (n) atomicAdd(bins + 4 * w + field, (unsigned long long)n);
+    }
+};
+constexpr int64_t kOpenEnd = INT64_MAX;
+__device__ __forceinline__ uint32_t field_of_op(uint32_t op) { return op == kOpEq ? 0u : op == kOpX ? 1u : op == kOpI ? 2u : 3u; }   // cl_pair_window's order
+
+struct WindowAcc {
+    int64_t w, lo, hi;          // the window the thread is in and its path-1 range [lo, hi); w < 0: none yet
+    uint32_t eq, x;
+    uint64_t ins, del;
+    __device__ WindowAcc() : w(-1), lo(0), hi(0), eq(0), x(0), ins(0), del(0) {}
+    __device__ void flush(const WindowBins& b) {
+        if (w >= 0) { b.add(w, 0, eq); b.add(w, 1, x); b.add(w, 2, ins); b.add(w, 3, del); }
+        eq = x = 0;
+        ins = del = 0;
+    }
+    __device__ void enter(const WindowBins& b, int64_t nw) {   // nw: unclamped window index
+        flush(b);
+        w = nw < b.last ? nw : b.last;
+        lo = w * b.width;
+        hi = w < b.last ? lo + b.width : kOpenEnd;
+    }
+    // move to the window of path-1 index i1 (at or after every index sought before)
+    __device__ void seek(const WindowBins& b, int64_t i1) {
+        if (w < 0) enter(b, i1 / b.width);
+        else if (i1 >= hi) enter(b, i1 - hi < b.width ? w + 1 : i1 / b.width);
+    }
+    __device__ void count(uint32_t op, int64_t cnt) {
+        eq += op == kOpEq ? (uint32_t)cnt : 0;
+        x += op == kOpX ? (uint32_t)cnt : 0;
+        ins += op == kOpI ? (uint64_t)cnt : 0;
+        del += op == kOpD ? (uint64_t)cnt : 0;
+    }
+};
+
+// The counts the lanes of a wave still hold at the end of a tile, added to the bins: lanes in the same window are neighbours (i1 does not
+// decrease along path 2), so the wave sums each segment of equal window with shuffles and the segment's last lane issues its atomics.
+__device__ __forceinline__ void wave_flush(const WindowBins& b, WindowAcc& acc) {
+    const unsigned lane = threadIdx.x & 63;
+    const int64_t up = shfl_up64(acc.w, 1);
+    int start = lane == 0 || up != acc.w ? (int)lane : 0;   // the first lane of this lane's segment, after the scan
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(start, d, 64);
+        if (lane >= d && o > start) start = o;
+    }
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const uint32_t eq = (uint32_t)__shfl_up((int)acc.eq, d, 64), x = (uint32_t)__shfl_up((int)acc.x, d, 64);
+        const uint64_t ins = (uint64_t)shfl_up64((int64_t)acc.ins, d), del = (uint64_t)shfl_up64((int64_t)acc.del, d);
+        if ((int)lane - (int)d >= start) { acc.eq += eq; acc.x += x; acc.ins += ins; acc.del += del; }
+    }
+    const int64_t down = (int64_t)__shfl_down((long long)acc.w, 1, 64);
+    if (lane != 63 && down == acc.w) acc.eq = acc.x = 0, acc.ins = acc.del = 0;   // not the segment's last lane
+    acc.flush(b);
+    acc.w = -1;
+}
+
+// Scan 1 as in induced_stats_kernel, then every thread adds its tokens to the windows they cover.  A D run is split base by base over its windows:
+// the part in the thread's window and the part in the run's last window go through the thread's registers; the whole windows in between get
+// `width` each, from the thread itself when they are few and from the 64 lanes of its wave otherwise (a run can cross more windows than a tile
+// has threads).  The run after the last match is added by the whole workgroup: its D run can be all of path 1.
+__global__ void __launch_bounds__(kThreads) induced_profile_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                                  const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                                  uint64_t width, cl_pair_window* __restrict__ windows) {
+    __shared__ MatchScan lds1[kWaves];
+    constexpr int64_t kInlineWindows = 4;
+    const ClInducedJob job = jobs[blockIdx.x];
+    const uint32_t* pos = tables + job.table;
+    PairView v{path_nodes + job.off1, path_nodes + job.off2, path_nodes + n_steps, label, n_nodes, (int64_t)job.n1, (int64_t)job.n2};
+    const WindowBins b{(unsigned long long*)(windows + job.text_off), (int64_t)width, (int64_t)job.text_cap - 1};
+    const unsigned lane = threadIdx.x & 63;
+    MatchScan c1 = MatchScan::ident();
+    for (int64_t base = 0; base < v.n2; base += kTile) {
+        const int64_t s0 = base + (int64_t)threadIdx.x * kItems;
+        uint32_t a[kItems];
+        MatchScan agg = MatchScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            a[r] = kNoPos;
+            if (s0 + r < v.n2) a[r] = pos[v.p2[s0 + r]];
+            if (a[r] != kNoPos) agg = combine(agg, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        MatchScan tot1;
+        MatchScan x = combine(c1, block_exclusive(agg, lds1, tot1));
+        c1 = combine(c1, tot1);
+        WindowAcc acc;
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            int64_t whole0 = 0, whole1 = 0;   // the whole windows [whole0, whole1) of this step's D run, left to the wave
+            if (a[r] != kNoPos) {
+                match_tokens_at(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt, int64_t i1, int64_t) {
+                    acc.seek(b, i1);
+                    if (op != kOpD || i1 + cnt <= acc.hi) { acc.count(op, cnt); return; }
+                    const int64_t end = i1 + cnt;
+                    acc.count(op, acc.hi - i1);
+                    const int64_t w0 = acc.w + 1, at = (end - 1) / b.width, w1 = at < b.last ? at : b.last;   // w0 <= w1: the run goes on past acc.hi
+                    if (w1 - w0 <= kInlineWindows) for (int64_t w = w0; w < w1; ++w) b.add(w, 3, (uint64_t)b.width);
+                    else { whole0 = w0; whole1 = w1; }
+                    acc.enter(b, w1);
+                    acc.count(op, end - acc.lo);
+                });
+                x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+            }
+            for (uint64_t m = __ballot(whole1 > whole0); m; m &= m - 1) {
+                const int src = __ffsll((unsigned long long)m) - 1;
+                const int64_t w0 = (int64_t)__shfl((long long)whole0, src, 64), w1 = (int64_t)__shfl((long long)whole1, src, 64);
+                for (int64_t w = w0 + lane; w < w1; w += 64) b.add(w, 3, (uint64_t)b.width);
+            }
+        }
+        wave_flush(b, acc);
+    }
+    // the run after the last match, as in induced_runs_kernel
+    const int64_t k = c1.cnt;
+    const int64_t e_last = k > 0 ? k - 1 + (c1.best > 0 ? c1.best : 0) : -1;
+    const int64_t g2 = v.n1 > e_last + 1 ? v.n1 - e_last - 1 : 0, g1 = v.n2 - 1 - c1.last;
+    gap_run_tokens_at(v, e_last, c1.last, g1, g2, [&](uint32_t op, int64_t cnt, int64_t i1, int64_t) {
+        const int64_t end = i1 + cnt, f = i1 / b.width, w0 = f < b.last ? f : b.last;
+        if (op != kOpD) {
+            if (threadIdx.x == 0) b.add(w0, field_of_op(op), (uint64_t)cnt);
+            return;
+        }
+        const int64_t at = (end - 1) / b.width, w1 = at < b.last ? at : b.last;
+        for (int64_t w = w0 + threadIdx.x; w <= w1; w += kThreads) {
+            const int64_t lo = w * b.width > i1 ? w * b.width : i1, hi = w < b.last && (w + 1) * b.width < end ? (w + 1) * b.width : end;
+            b.add(w, 3, (uint64_t)(hi - lo));
+        }
+    });
+}
+
+// ---------------------------------------------------------------- gap events ------------------------------------------------------------------
+struct CountScan {
+    int64_t n;
+    static __device__ CountScan ident() { return {0}; }
+    __device__ CountScan up(unsigned d) const { return {shfl_up64(n, d)}; }
+};
+__device__ __forceinline__ CountScan combine(const CountScan& a, const CountScan& b) { return {a.n + b.n}; }
+
+// Two passes like induced_runs_kernel.  Counting: every thread counts its D and I tokens of at least min_len bases over all tiles, one workgroup sum
+// at the end.  Writing: per tile an exclusive sum of the threads' counts (at most 8 each) places each thread's events behind the tile carry, so
+// a pair's events are in CIGAR order.  job.text_off / text_cap: the pair's first event and their number, in elements of `events`.
+template <bool kWrite>
+__global__ void __launch_bounds__(kThreads) induced_events_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                                 const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                                 uint64_t min_len, int64_t* __restrict__ n_events, cl_gap_event* __restrict__ events) {
+    __shared__ MatchScan lds1[kWaves];
+    __shared__ CountScan lds2[kWaves];
+    const ClInducedJob job = jobs[blockIdx.x];
+    const uint32_t* pos = tables + job.table;
+    PairView v{path_nodes + job.off1, path_nodes + job.off2, path_nodes + n_steps, label, n_nodes, (int64_t)job.n1, (int64_t)job.n2};
+    cl_gap_event* out = kWrite ? events + job.text_off : nullptr;
+    const int64_t cap = kWrite ? (int64_t)job.text_cap : 0, len_min = (int64_t)min_len;
+    auto is_event = [&](uint32_t op, int64_t cnt) { return (op == kOpD || op == kOpI) && cnt >= len_min; };
+    auto put = [&](int64_t at, uint32_t op, int64_t cnt, int64_t i1, int64_t i2) {
+        if (at < cap) out[at] = cl_gap_event{(uint64_t)i1, (uint64_t)i2, (uint64_t)cnt, op == kOpI ? 1u : 0u, 0u};
+    };
+    MatchScan c1 = MatchScan::ident();
+    int64_t carry = 0;   // counting: this thread's events so far; writing: the pair's events in the tiles before
+    for (int64_t base = 0; base < v.n2; base += kTile) {
+        const int64_t s0 = base + (int64_t)threadIdx.x * kItems;
+        uint32_t a[kItems];
+        MatchScan agg = MatchScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            a[r] = kNoPos;
+            if (s0 + r < v.n2) a[r] = pos[v.p2[s0 + r]];
+            if (a[r] != kNoPos) agg = combine(agg, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        MatchScan tot1;
+        const MatchScan pre1 = combine(c1, block_exclusive(agg, lds1, tot1));
+        c1 = combine(c1, tot1);
+        int64_t mine = 0;
+        MatchScan x = pre1;
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            if (a[r] == kNoPos) continue;
+            match_tokens_at(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt, int64_t, int64_t) { mine += is_event(op, cnt); });
+            x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        if (!kWrite) { carry += mine; continue; }
+        CountScan tot2;
+        int64_t at = carry + block_exclusive(CountScan{mine}, lds2, tot2).n;
+        carry += tot2.n;
+        x = pre1;
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            if (a[r] == kNoPos) continue;
+            match_tokens_at(v, x, s0 + r, (int64_t)a[r], [&](uint32_t op, int64_t cnt, int64_t i1, int64_t i2) {
+                if (is_event(op, cnt)) put(at++, op, cnt, i1, i2);
+            });
+            x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+    }
+    if (!kWrite) {
+        CountScan tot2;
+        block_exclusive(CountScan{carry}, lds2, tot2);
+        carry = tot2.n;
+    }
+    if (threadIdx.x != 0) return;
+    // the run after the last match, as in induced_runs_kernel
+    const int64_t k = c1.cnt;
+    const int64_t e_last = k > 0 ? k - 1 + (c1.best > 0 ? c1.best : 0) : -1;
+    const int64_t g2 = v.n1 > e_last + 1 ? v.n1 - e_last - 1 : 0, g1 = v.n2 - 1 - c1.last;
+    gap_run_tokens_at(v, e_last, c1.last, g1, g2, [&](uint32_t op, int64_t cnt, int64_t i1, int64_t i2) {
+        if (!is_event(op, cnt)) return;
+        if (kWrite) put(carry, op, cnt, i1, i2);
+        ++carry;
+    });
+    if (!kWrite) n_events[blockIdx.x] = carry;
+}
+
 // pos[path1[i]] = i; a node met twice leaves one of its positions behind, which the check reads back
 __global__ void induced_scatter_kernel(const uint32_t* __restrict__ p1, uint64_t n1, uint32_t* __restrict__ pos) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * blockDim.x) pos[p1[i]] = (uint32_t)i;
@@ -393,5 +639,20 @@ hipError_t cl_launch_induced_stats(const ClInducedJob* jobs, uint32_t n_jobs, co
                                    const uint32_t* tables, cl_pair_stats* stats, hipStream_t stream) {
     if (n_jobs == 0) return hipSuccess;
     hipLaunchKernelGGL(induced_stats_kernel, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, stats);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_profile(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                     const uint32_t* tables, uint64_t window, cl_pair_window* windows, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(induced_profile_kernel, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, window, windows);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_events(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
+                                    uint64_t n_nodes, const uint32_t* tables, uint64_t min_len, int64_t* n_events, cl_gap_event* events, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    if (write) hipLaunchKernelGGL(induced_events_kernel<true>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, min_len, n_events, events);
+    else hipLaunchKernelGGL(induced_events_kernel<false>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, min_len, n_events, events);
     return hipGetLastError();
 }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 16   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 17   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -659,6 +659,29 @@ typedef struct cl_pair_stats {
 } cl_pair_stats;
 int cl_induced_pairwise_stat(const cl_base_graph* graph, uint64_t path1, uint64_t path2, cl_pair_stats* out);
 int cl_induced_pairwise_stats(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, cl_pair_stats* out /* [n_pairs] */);
+/* The same alignment resolved by position, again defined on the text of cl_induced_pairwise_cigar(graph, path1, path2) and made without it.  Read
+ * the CIGAR left to right with i1 = i2 = 0; '=' and 'X' advance both, 'D' advances i1 (path 1), 'I' advances i2 (path 2).
+ *   Profile: n_win = max(1, ceil(n1 / window)) windows of `window` (>= 1) bases of path 1 (n1: its steps).  A column belongs to window
+ *     min(i1 / window, n_win - 1) with i1 taken before the column: an 'I' column lies in the window of the path-1 base it stands in front of,
+ *     trailing insertions lie in the last window, and so do the columns whose path-1 index runs past n1 (path 2 meeting path 1's nodes out of
+ *     order or twice).  A cl_pair_window counts the columns of each letter; a long 'D' run is split base by base over the windows it crosses.
+ *     Summed over a pair's windows they are the pair's cl_pair_stats eq / x / ins / del.
+ *   Events: every 'I' or 'D' run of at least min_len (>= 1) bases, in CIGAR order, with i1 and i2 at its first column.  op 0: 'D', op 1: 'I'.
+ *     An unequal double gap is two events, the 'D' first, with the same pos2.
+ * cl_induced_pairwise_profile / cl_induced_gap_events: host only, the definitions; *out is malloc'ed (never NULL on success).
+ * cl_induced_pairwise_profiles / cl_induced_gap_events_batch: every (pairs[2k], pairs[2k+1]) in one device pass each (induced_kernels.hip: no text);
+ * *out is one malloc'ed buffer with the pairs' windows / events back to back, offsets_out[n_pairs + 1] where each pair's begin, in elements, and
+ * the end.  Pairs may repeat, (p, p) is allowed; error codes as cl_induced_pairwise_stats (the first failing pair decides), and
+ * CL_ERR_INVALID_ARGUMENT for window == 0 or min_len == 0.  Device memory beyond the graph's paths and labels: at most 256 MB of position tables
+ * and 256 MB of windows or events (or one pair's) at a time. */
+typedef struct cl_pair_window { uint64_t eq, x, ins, del; } cl_pair_window;
+typedef struct cl_gap_event { uint64_t pos1, pos2, len; uint32_t op, reserved /* 0 */; } cl_gap_event;
+int cl_induced_pairwise_profile(const cl_base_graph* graph, uint64_t path1, uint64_t path2, uint64_t window, cl_pair_window** out, uint64_t* n_win_out);
+int cl_induced_gap_events(const cl_base_graph* graph, uint64_t path1, uint64_t path2, uint64_t min_len, cl_gap_event** out, uint64_t* n_out);
+int cl_induced_pairwise_profiles(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, uint64_t window, cl_pair_window** out,
+                                 uint64_t* offsets_out /* [n_pairs + 1] */);
+int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, uint64_t min_len, cl_gap_event** out,
+                                uint64_t* offsets_out /* [n_pairs + 1] */);
 /* The -A output of the CLI after cyclisation (src/core.cpp:537-545): output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), graph,
  * path1, path2) (src/alignment.cpp:569-904) — blocks of colinear alignment between the two paths of a graph that may have cycles; name1 / name2
  * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
