@@ -523,6 +523,44 @@ def induced_gap_events_batch(graph, pairs, min_len, ctx):
     return _induced_positions_batch("cl_induced_gap_events_batch", graph, pairs, min_len, ctx, GAP_EVENT_DTYPE, 1, (-1,))
 
 
+PAIR_AGREEMENT_FIELDS = ("aligned_a", "aligned_b", "shared", "eq_a", "eq_b", "shared_eq", "n1", "n2")   # cl_pair_agreement, in the struct's order
+
+
+class PairAgreement(C.Structure):
+    """cl_pair_agreement: two graphs' alignments of one pair of sequences compared (64 bytes)"""
+    _fields_ = [(k, C.c_uint64) for k in PAIR_AGREEMENT_FIELDS]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in PAIR_AGREEMENT_FIELDS}
+
+
+def induced_pairwise_agreement(graph_a, a1, a2, graph_b, b1, b2):
+    """cl_induced_pairwise_agreement (host only): the aligned pairs of induced_pairwise_cigar(graph_a, a1, a2) and of
+    induced_pairwise_cigar(graph_b, b1, b2) — the same two sequences in two graphs — counted and intersected; a dict over PAIR_AGREEMENT_FIELDS"""
+    lib = load_library()
+    ga, gb, out = graph_a.as_c(), graph_b.as_c(), PairAgreement()
+    lib.cl_induced_pairwise_agreement.restype = C.c_int
+    lib.cl_induced_pairwise_agreement.argtypes = [C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64, C.POINTER(BaseGraphC), C.c_uint64, C.c_uint64,
+                                                  C.POINTER(PairAgreement)]
+    rc = lib.cl_induced_pairwise_agreement(C.byref(ga), int(a1), int(a2), C.byref(gb), int(b1), int(b2), C.byref(out))
+    if rc != 0:
+        raise ClError(rc, "cl_induced_pairwise_agreement")
+    return out.as_dict()
+
+
+def induced_pairwise_agreements(graph_a, graph_b, quads, ctx):
+    """cl_induced_pairwise_agreements: induced_pairwise_agreement of every (a1, a2, b1, b2) row of `quads` in two device passes on Context ctx; a
+    uint64 array [len(quads), 8] with PAIR_AGREEMENT_FIELDS as columns.  Raises ClError with the host function's code for the first failing quad."""
+    lib = load_library()
+    quads = np.ascontiguousarray(np.asarray(quads, np.uint64).reshape(-1, 4))
+    n = len(quads)
+    ga, gb, out = graph_a.as_c(), graph_b.as_c(), np.zeros((n, 8), np.uint64)
+    lib.cl_induced_pairwise_agreements.restype = C.c_int
+    lib.cl_induced_pairwise_agreements.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.POINTER(BaseGraphC), C.c_void_p, C.c_uint64, C.c_void_p]
+    ctx._check(lib.cl_induced_pairwise_agreements(ctx.handle, C.byref(ga), C.byref(gb), quads.ctypes.data, n, out.ctypes.data))
+    return out
+
+
 def alignment_distances(stats, n):
     """cl_alignment_distances (host only): the [n, n] float64 matrix d = 1 - 2 eq / (2 eq + 2 x + ins + del) of the n * (n - 1) / 2 rows of `stats`
     (induced_pairwise_stats of the pairs (a, b), a < b, a outer)"""
@@ -1300,7 +1338,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 17    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 18    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1517,6 +1555,7 @@ EXPORTED_SYMBOLS = [
     "cl_kmer_distances_compute", "cl_kmer_distances_free", "cl_neighbor_joining_newick", "cl_infer_guide_tree",
     "cl_induced_pairwise_stat", "cl_induced_pairwise_stats", "cl_alignment_distances", "cl_refine_guide_tree",
     "cl_induced_pairwise_profile", "cl_induced_pairwise_profiles", "cl_induced_gap_events", "cl_induced_gap_events_batch",
+    "cl_induced_pairwise_agreement", "cl_induced_pairwise_agreements",
 ]
 
 

@@ -11,6 +11,8 @@
 //   - --pair-profile (with --window) and --pair-events (with --min-event) write, for every pair of sequences, the induced alignment's columns per
 //     window of the first sequence and its long insertions and deletions with their positions (cl_induced_pairwise_profiles,
 //     cl_induced_gap_events_batch on the printed graph); not with -c, whose final graph has cycles;
+//   - --compare-to GFA with --pair-agreement FILE writes, for every pair of sequences, how many aligned base pairs the printed graph shares with a
+//     baseline graph of the same sequences (cl_induced_pairwise_agreements); --graph GFA compares a graph that is already there instead of aligning;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -234,6 +236,93 @@ bool write_pair_positions(cl_context* ctx, const char* gfa, uint64_t gfa_len, co
     return true;
 }
 
+// a GFA text as the graph the comparisons read (cl_read_gfa, as above) with its path names
+struct NamedGraph {
+    cl_owned_base_graph* owned = nullptr;
+    cl_base_graph g;
+    std::vector<std::string> names;
+    NamedGraph() = default;
+    NamedGraph(const NamedGraph&) = delete;
+    NamedGraph& operator=(const NamedGraph&) = delete;
+    ~NamedGraph() { if (owned) cl_owned_base_graph_free(owned); }
+    bool load(const char* text, uint64_t len) {
+        char** path_names = nullptr;
+        uint64_t n_paths = 0;
+        if (cl_read_gfa(text, len, 1, &owned, &path_names, &n_paths)) return false;
+        for (uint64_t p = 0; p < n_paths; ++p) { names.emplace_back(path_names[p]); free(path_names[p]); }
+        free(path_names);
+        cl_owned_base_graph_view(owned, &g);
+        return true;
+    }
+    uint64_t steps(uint64_t p) const { return g.path_off[p + 1] - g.path_off[p]; }
+    const std::string* repeated_name() const {   // a name two paths carry: a sequence could not be found by it
+        std::vector<const std::string*> sorted;
+        for (const std::string& nm : names) sorted.push_back(&nm);
+        std::sort(sorted.begin(), sorted.end(), [](const std::string* x, const std::string* y) { return *x < *y; });
+        for (size_t i = 1; i < sorted.size(); ++i) if (*sorted[i] == *sorted[i - 1]) return sorted[i];
+        return nullptr;
+    }
+    bool has_cycles() const {   // a path that meets a node twice
+        std::vector<uint64_t> seen(g.n_nodes, 0);
+        for (uint64_t p = 0; p < g.n_paths; ++p)
+            for (uint64_t i = g.path_off[p]; i < g.path_off[p + 1]; ++i) {
+                if (seen[g.path_nodes[i]] == p + 1) return true;
+                seen[g.path_nodes[i]] = p + 1;
+            }
+        return false;
+    }
+};
+
+// --compare-to / --pair-agreement: every pair (p, q), p < q, of the printed graph's paths against the same two sequences in the baseline, found there
+// by name; names as --pair-stats writes them.  The baseline is graph a of cl_induced_pairwise_agreements: aligned_base, matches_base are its columns
+bool write_pair_agreement(cl_context* ctx, const NamedGraph& printed, const NamedGraph& base, const std::string& file, std::string& err) {
+    const uint64_t n = printed.names.size();
+    std::vector<uint64_t> in_base(n);
+    for (uint64_t p = 0; p < n; ++p) {
+        const auto it = std::find(base.names.begin(), base.names.end(), printed.names[p]);
+        if (it == base.names.end()) { err = "the baseline graph has no path " + printed.names[p]; return false; }
+        const uint64_t q = (uint64_t)(it - base.names.begin());
+        bool same = printed.steps(p) == base.steps(q);
+        for (uint64_t i = 0; same && i < printed.steps(p); ++i)
+            same = printed.g.label[printed.g.path_nodes[printed.g.path_off[p] + i]] == base.g.label[base.g.path_nodes[base.g.path_off[q] + i]];
+        if (!same) { err = "path " + printed.names[p] + " spells another sequence in the baseline graph"; return false; }
+        in_base[p] = q;
+    }
+    std::vector<uint64_t> quads;
+    for (uint64_t p = 0; p < n; ++p)
+        for (uint64_t q = p + 1; q < n; ++q) quads.insert(quads.end(), {in_base[p], in_base[q], p, q});
+    const uint64_t n_quads = quads.size() / 4;
+    std::vector<cl_pair_agreement> got(n_quads);
+    if (cl_induced_pairwise_agreements(ctx, &base.g, &printed.g, quads.data(), n_quads, got.data())) {
+        const char* e = cl_last_error(ctx);
+        err = std::string("agreement with the baseline graph: ") + (e && *e ? e : "failed");
+        return false;
+    }
+    std::string tsv = "sample1\tsample2\taligned_base\taligned\tshared\tmatches_base\tmatches\tshared_matches\n";
+    uint64_t aligned_base = 0, aligned = 0, shared = 0;
+    for (uint64_t k = 0; k < n_quads; ++k) {
+        std::string lead = printed.names[quads[4 * k + 2]] + "\t" + printed.names[quads[4 * k + 3]];
+        for (char& c : lead) if (c == '/') c = '_';
+        const cl_pair_agreement& r = got[k];
+        char num[200];
+        snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r.aligned_a, (unsigned long long)r.aligned_b,
+                 (unsigned long long)r.shared, (unsigned long long)r.eq_a, (unsigned long long)r.eq_b, (unsigned long long)r.shared_eq);
+        tsv += lead;
+        tsv += num;
+        aligned_base += r.aligned_a; aligned += r.aligned_b; shared += r.shared;
+    }
+    std::ofstream out(file, std::ios::binary);
+    if (out) out.write(tsv.data(), (std::streamsize)tsv.size());
+    out.close();
+    if (!out) { err = "could not write to " + file; return false; }
+    char line[256];
+    snprintf(line, sizeof(line), "Agreement with the baseline over %llu pair(s): recall %.6f (%llu shared of %llu aligned there), precision %.6f (of %llu aligned here).",
+             (unsigned long long)n_quads, aligned_base ? (double)shared / (double)aligned_base : 1.0, (unsigned long long)shared, (unsigned long long)aligned_base,
+             aligned ? (double)shared / (double)aligned : 1.0, (unsigned long long)aligned);
+    log_line(LOG_BASIC, line);
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -272,11 +361,14 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --window INT                With --pair-profile, the window in bases of the first sequence [1000]\n");
     fprintf(o, " --pair-events FILE          Write every insertion and deletion of at least --min-event bases between two sequences, with its positions, to FILE (which must not exist yet; not with -c)\n");
     fprintf(o, " --min-event INT             With --pair-events, the least length of an insertion or deletion that is written [50]\n");
+    fprintf(o, " --compare-to GFA            With --pair-agreement, the baseline graph of the same sequences: an earlier run's, the reference's, a truth graph\n");
+    fprintf(o, " --pair-agreement FILE       Write the aligned base pairs of every pair of sequences here, in the baseline and in both, to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --graph GFA                 With --compare-to and --pair-agreement, compare GFA as the graph this run would have printed: nothing is aligned or printed\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
     fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats, --dist-out, --pair-profile, --window,\n");
-    fprintf(o, "--pair-events and --min-event are added; -v gates this tool's own\n");
+    fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement and --graph are added; -v gates this tool's own\n");
     fprintf(o, "progress lines. See README.md.\n");
 }
 
@@ -299,13 +391,15 @@ int run(int argc, char** argv) {
     cl_config* cfg = own.cfg;
 
     std::string config_name;
-    std::string tree_out, pair_stats, dist_out, refine_arg, pair_profile, pair_events, window_arg, min_event_arg;
+    std::string tree_out, pair_stats, dist_out, refine_arg, pair_profile, pair_events, window_arg, min_event_arg, compare_to, pair_agreement, graph_name;
+    bool have_graph = false;
     bool force_gfa_output = false, generate_config = false, infer_tree = false, have_window = false, have_min_event = false;
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
            OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009,
-           OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013 };
+           OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013,
+           OPT_COMPARE_TO = 1014, OPT_PAIR_AGREEMENT = 1015, OPT_GRAPH = 1016 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -337,6 +431,9 @@ int run(int argc, char** argv) {
         {"window", required_argument, nullptr, OPT_WINDOW},
         {"pair-events", required_argument, nullptr, OPT_PAIR_EVENTS},
         {"min-event", required_argument, nullptr, OPT_MIN_EVENT},
+        {"compare-to", required_argument, nullptr, OPT_COMPARE_TO},
+        {"pair-agreement", required_argument, nullptr, OPT_PAIR_AGREEMENT},
+        {"graph", required_argument, nullptr, OPT_GRAPH},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -378,6 +475,9 @@ int run(int argc, char** argv) {
         case OPT_WINDOW: window_arg = optarg; have_window = true; break;
         case OPT_PAIR_EVENTS: pair_events = optarg; break;
         case OPT_MIN_EVENT: min_event_arg = optarg; have_min_event = true; break;
+        case OPT_COMPARE_TO: compare_to = optarg; break;
+        case OPT_PAIR_AGREEMENT: pair_agreement = optarg; break;
+        case OPT_GRAPH: graph_name = optarg; have_graph = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -402,6 +502,19 @@ int run(int argc, char** argv) {
         const std::string text = generate(cfg);
         fwrite(text.data(), 1, text.size(), stdout);
         return fflush(stdout) == 0 ? 0 : fail("could not write the config to standard output");
+    }
+
+    // --graph stands in for the whole run: it goes with the two comparison options and with nothing that reads an input or writes another output
+    if (have_graph) {
+        if (compare_to.empty() || pair_agreement.empty()) return fail("--graph needs --compare-to and --pair-agreement");
+        if (n_positional == 1) return fail("--graph cannot be combined with a FASTA: it takes the place of the alignment");
+        if (!config_value(cfg, "tree_name").empty() || infer_tree || !refine_arg.empty()) return fail("--graph cannot be combined with a guide tree (-T, --infer-tree, --refine-tree)");
+        if (!config_name.empty()) return fail("--graph cannot be combined with a config file (-C)");
+        if (config_value(cfg, "restart") == "true") return fail("--graph cannot be combined with a restart (-R)");
+        for (const char* name : {"all_pairs_prefix", "subproblems_prefix", "subalignments_filepath", "bonds_prefix"})
+            if (!config_value(cfg, name).empty()) return fail("--graph cannot be combined with another output option (-A, -S, -s, --bond-prefix)");
+        if (!tree_out.empty() || !pair_stats.empty() || !dist_out.empty() || !pair_profile.empty() || !pair_events.empty() || have_window || have_min_event)
+            return fail("--graph cannot be combined with another output option (--tree-out, --pair-stats, --dist-out, --pair-profile, --pair-events)");
     }
 
     if (!config_name.empty()) {
@@ -441,6 +554,39 @@ int run(int argc, char** argv) {
     const bool pair_positions = !pair_profile.empty() || !pair_events.empty();
     if (pair_positions && config_value(cfg, "cyclize_tandem_duplications") == "true")
         return fail("--pair-profile and --pair-events cannot be combined with -c: the final graph then has cycles");
+    // --compare-to / --pair-agreement, checked the same way; the baseline is read here: what is wrong with it needs no other input
+    if (compare_to.empty() != pair_agreement.empty()) return fail(compare_to.empty() ? "--pair-agreement needs --compare-to" : "--compare-to needs --pair-agreement");
+    const bool agreement = !pair_agreement.empty();
+    if (agreement && std::ifstream(pair_agreement).good()) return fail("Pair agreement file already exists: " + pair_agreement);
+    if (agreement && (pair_agreement == pair_profile || pair_agreement == pair_events || pair_agreement == pair_stats || pair_agreement == dist_out))
+        return fail("--pair-agreement names the file of another output option");
+    if (agreement && config_value(cfg, "cyclize_tandem_duplications") == "true")
+        return fail("--compare-to and --pair-agreement cannot be combined with -c: the final graph then has cycles");
+    NamedGraph baseline, given;
+    auto load_graph = [&](const std::string& name, const char* what, NamedGraph& into, std::string& err) {
+        std::string text;
+        if (!read_input(name, text, err)) return false;
+        if (!into.load(text.data(), text.size())) { err = std::string("cannot read the ") + what + " graph from " + name + ": not a GFA this tool writes"; return false; }
+        if (const std::string* twice = into.repeated_name()) { err = std::string("the ") + what + " graph " + name + " has two paths named " + *twice; return false; }
+        if (into.has_cycles()) { err = std::string("the ") + what + " graph " + name + " has cycles: a path meets a node twice"; return false; }
+        return true;
+    };
+    if (agreement) {
+        std::string err;
+        if (compare_to == "-" || graph_name == "-") return fail("--compare-to and --graph take files, not standard input");
+        if (!load_graph(compare_to, "baseline", baseline, err)) return fail(err);
+        if (have_graph && !load_graph(graph_name, "given", given, err)) return fail(err);
+    }
+    if (have_graph) {   // no FASTA, no alignment, nothing on standard output: the given graph against the baseline
+        g_level = atoi(config_value(cfg, "logging_level").c_str());
+        const int device = devices.empty() ? 0 : devices[0];
+        own.ctx = cl_context_create(device);
+        if (!own.ctx) return fail("no usable GPU: " + lib_error());
+        std::string err;
+        if (!write_pair_agreement(own.ctx, given, baseline, pair_agreement, err)) return fail(err);
+        log_line(LOG_MINIMAL, "Compared " + graph_name + " with " + compare_to + ", exiting.");
+        return 0;
+    }
     // --dist-out alone passes the rows through a file of its own next to FILE, which must not be anybody else's
     const std::string dist_tmp = !dist_out.empty() && pair_stats.empty() ? dist_out + ".pair-stats.tmp" : std::string();
     if (!dist_tmp.empty() && std::ifstream(dist_tmp).good()) return fail("--dist-out would overwrite " + dist_tmp + ": remove it or give --pair-stats");
@@ -475,6 +621,8 @@ int run(int argc, char** argv) {
                     " sequence(s), cannot form an alignment");
     if (pair_positions && n_sequences == 2 && !force_gfa_output)
         return fail("--pair-profile and --pair-events need --force-gfa-output for two sequences: they read the graph that is printed");
+    if (agreement && n_sequences == 2 && !force_gfa_output)
+        return fail("--compare-to and --pair-agreement need --force-gfa-output for two sequences: they read the graph that is printed");
     if (!dist_out.empty()) {   // the rows name sequences as -A names its files: two names that differ only in '/' and '_' could not be told apart
         std::vector<std::string> flat = sequence_names;
         for (std::string& nm : flat) for (char& c : nm) if (c == '/') c = '_';
@@ -564,9 +712,15 @@ int run(int argc, char** argv) {
     const bool written = fwrite(text, 1, len, stdout) == len && fflush(stdout) == 0;
     std::string positions_err;
     const bool positions_ok = !written || !pair_positions || write_pair_positions(own.ctx, text, len, pair_profile, window, pair_events, min_event, positions_err);
+    bool agreement_ok = true;
+    if (written && positions_ok && agreement) {
+        NamedGraph printed;
+        agreement_ok = printed.load(text, len) ? write_pair_agreement(own.ctx, printed, baseline, pair_agreement, positions_err)
+                                               : (positions_err = "cannot read back the alignment graph", false);
+    }
     free(text);
     if (!written) return fail("could not write the alignment to standard output");
-    if (!positions_ok) return fail(positions_err);
+    if (!positions_ok || !agreement_ok) return fail(positions_err);
     if (!dist_out.empty()) {
         std::string err;
         const bool ok = write_distances(stats_file, sequence_names, dist_out, err);

@@ -7,6 +7,9 @@
 //                               the same alignments by position: per window of path 1 the columns of each letter, and the I / D runs of a least
 //                               length with their places; one kernel each over the same frame, no text; host restatements:
 //                               cl_induced_pairwise_profile, cl_induced_gap_events
+//   cl_induced_pairwise_agreements
+//                               two graphs' alignments of the same pairs compared: a partner pass over graph a and an agreement pass over graph b
+//                               through the same frame, each graph on the device once; host restatement: cl_induced_pairwise_agreement
 //   cl_induced_cyclic_maf       output_maf(induced_cyclic_pairwise_alignment(...)) (src/alignment.cpp:229-904), the output after cyclisation.
 //                               Host code: its core is a Hunt-Szymanski LCS, a dependent chain of binary searches over a threshold row
 //                               (DESIGN.md §9); the caller runs pairs in parallel, as the reference does (core.cpp:554-591).
@@ -35,6 +38,8 @@ constexpr uint64_t kGap = ~(uint64_t)0;
 // events of an event write pass.  A chunk also holds at most kChunkPairs pairs.
 constexpr uint64_t kChunkTableBytes = 256ull << 20, kChunkTextBytes = 256ull << 20, kChunkPairs = 2048;
 constexpr uint64_t kChunkWindows = (256ull << 20) / sizeof(cl_pair_window), kChunkEvents = (256ull << 20) / sizeof(cl_gap_event);
+// cl_induced_pairwise_agreements: the partner words of one group of quads, 4 bytes per step of each quad's path 2 (one quad may exceed it alone)
+constexpr uint64_t kChunkPartnerBytes = 256ull << 20;
 
 // ---------------------------------------------------------------- the cyclic MAF -------------------------------------------------------------
 using Pair = std::pair<uint64_t, uint64_t>;   // (index on path 1, index on path 2), kGap: none
@@ -384,41 +389,80 @@ struct InducedChunk {
     const uint32_t* d_tables;
 };
 
-// The frame of cl_induced_pairwise_cigars, _stats, _profiles and cl_induced_gap_events_batch: the checks the host makes (cl_induced_pairwise_cigar's order), the
-// graph on the device, the pairs ordered by first path and cut into chunks, each chunk's position tables (scatter + check), then pass(chunk)
-// for the entry point's own kernels and copies, and at the end the code of the first failing pair.
-template <class Pass>
-int induced_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, Pass&& pass) {
-    // what the host decides (cl_induced_pairwise_cigar's order): a path index out of range, then a path-1 node id out of range; a repeated path-1
-    // node is found on the device; then a path-2 node id out of range
-    std::vector<int8_t> bad_ids(g->n_paths, -1);
-    auto ids_bad = [&](uint64_t p) {
+// A device array that is released where it goes out of scope (DevBuf itself has no destructor)
+template <class T>
+struct ScopedBuf : DevBuf<T> {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf&) = delete;
+    ScopedBuf& operator=(const ScopedBuf&) = delete;
+    ~ScopedBuf() { this->release(); }
+};
+
+// A graph on the device for the passes over pairs of its paths: paths and labels, uploaded once and only when a pair needs them, and what is
+// known about each path — node ids out of range (found on the host, once per path) and nodes met twice (found on the device with the tables)
+struct InducedGraph {
+    cl_context* ctx;
+    const cl_base_graph* g;
+    uint64_t n_steps;
+    ScopedBuf<uint32_t> d_nodes;
+    ScopedBuf<uint8_t> d_label;
+    bool on_device = false;
+    std::vector<int8_t> bad_ids;
+    std::vector<uint8_t> repeated, host_checked;
+    std::vector<uint64_t> seen;
+    InducedGraph(cl_context* c, const cl_base_graph* graph)
+        : ctx(c), g(graph), n_steps(graph->path_off[graph->n_paths]), bad_ids(graph->n_paths, -1), repeated(graph->n_paths, 0), host_checked(graph->n_paths, 0) {}
+    bool ids_bad(uint64_t p) {
         if (bad_ids[p] < 0) {
             bad_ids[p] = 0;
             for (uint64_t i = g->path_off[p]; i < g->path_off[p + 1]; ++i) if (g->path_nodes[i] >= g->n_nodes) { bad_ids[p] = 1; break; }
             if (g->path_off[p + 1] - g->path_off[p] >= 0xFFFFFFFFull) bad_ids[p] = 1;   // positions are 32-bit words in the table
         }
         return bad_ids[p] == 1;
-    };
-    std::vector<int> pre(n_pairs, CL_OK);
-    std::vector<uint64_t> todo;   // pairs whose path 1 gets a position table, ordered by path 1
-    for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t a = pairs[2 * k], b = pairs[2 * k + 1];
-        if (a >= g->n_paths || b >= g->n_paths) { pre[k] = CL_ERR_INVALID_ARGUMENT; continue; }
-        if (ids_bad(a)) { pre[k] = CL_ERR_CYCLIC_GRAPH; continue; }
-        todo.push_back(k);
     }
-    std::stable_sort(todo.begin(), todo.end(), [&](uint64_t x, uint64_t y) { return pairs[2 * x] < pairs[2 * y]; });
-    std::vector<uint8_t> repeated(g->n_paths, 0);
-    const uint64_t n_steps = g->path_off[g->n_paths];
-    DevBuf<uint32_t> d_nodes;
-    DevBuf<uint8_t> d_label;
-    int rc;
-    if (!todo.empty()) {
+    int upload() {
+        if (on_device) return CL_OK;
+        int rc;
         if ((rc = d_nodes.alloc(ctx, n_steps)) || (rc = d_label.alloc(ctx, g->n_nodes))) return rc;
         HIP_TRY(ctx, cl_copy_sync(ctx, d_nodes.p, g->path_nodes, n_steps * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(ctx, cl_copy_sync(ctx, d_label.p, g->label, g->n_nodes, hipMemcpyHostToDevice));
+        on_device = true;
+        return CL_OK;
     }
+    // the device's repeat check on the host, for a first path no chunk held
+    void find_repeats(uint64_t p) {
+        if (p >= g->n_paths || ids_bad(p) || repeated[p] || host_checked[p]) return;
+        host_checked[p] = 1;
+        if (seen.empty()) seen.assign(g->n_nodes, 0);   // seen[v]: 1 + the last path checked here that holds node v
+        for (uint64_t i = g->path_off[p]; i < g->path_off[p + 1] && !repeated[p]; ++i) {
+            repeated[p] = seen[g->path_nodes[i]] == p + 1;
+            seen[g->path_nodes[i]] = p + 1;
+        }
+    }
+    // what cl_induced_pairwise_cigar returns for (a, b), once the device has seen a's table: a path index out of range, then a path-1 node id out
+    // of range or met twice, then a path-2 node id out of range
+    int code(uint64_t a, uint64_t b) {
+        if (a >= g->n_paths || b >= g->n_paths) return CL_ERR_INVALID_ARGUMENT;
+        if (ids_bad(a) || repeated[a]) return CL_ERR_CYCLIC_GRAPH;
+        return ids_bad(b) ? CL_ERR_INVALID_ARGUMENT : CL_OK;
+    }
+};
+
+// Chunks of these pairs of a graph on the device: the pairs the host does not refuse, ordered by first path and cut into chunks, each chunk's
+// position tables (scatter + check), then pass(chunk) for the entry point's own kernels and copies.  Afterwards dg.code() holds for every pair.
+template <class Pass>
+int induced_chunks(InducedGraph& dg, const uint64_t* pairs, uint64_t n_pairs, Pass&& pass) {
+    cl_context* ctx = dg.ctx;
+    const cl_base_graph* g = dg.g;
+    std::vector<uint64_t> todo;   // pairs whose path 1 gets a position table, ordered by path 1
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        const uint64_t a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a >= g->n_paths || b >= g->n_paths || dg.ids_bad(a)) continue;
+        todo.push_back(k);
+    }
+    std::stable_sort(todo.begin(), todo.end(), [&](uint64_t x, uint64_t y) { return pairs[2 * x] < pairs[2 * y]; });
+    int rc;
+    if (!todo.empty() && (rc = dg.upload())) return rc;
     const uint64_t table_bytes = std::max<uint64_t>(g->n_nodes, 1) * sizeof(uint32_t);
     for (size_t c0 = 0; c0 < todo.size();) {
         // one chunk: up to kChunkPairs pairs whose first paths' tables fit in kChunkTableBytes (at least one first path)
@@ -432,18 +476,18 @@ int induced_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs
             }
             ++c1;
         }
-        DevBuf<uint32_t> d_tables, d_rep;
+        ScopedBuf<uint32_t> d_tables, d_rep;
         if ((rc = d_tables.alloc(ctx, firsts.size() * (table_bytes / sizeof(uint32_t))))) return rc;
         if ((rc = d_rep.alloc(ctx, firsts.size()))) return rc;
         HIP_TRY(ctx, hipMemsetAsync(d_rep.p, 0, firsts.size() * sizeof(uint32_t), ctx->stream));
         for (size_t f = 0; f < firsts.size(); ++f)
-            HIP_TRY(ctx, cl_launch_induced_table(d_nodes.p + g->path_off[firsts[f]], g->path_off[firsts[f] + 1] - g->path_off[firsts[f]],
+            HIP_TRY(ctx, cl_launch_induced_table(dg.d_nodes.p + g->path_off[firsts[f]], g->path_off[firsts[f] + 1] - g->path_off[firsts[f]],
                                                  d_tables.p + f * (table_bytes / sizeof(uint32_t)), g->n_nodes, d_rep.p + f, ctx->stream));
-        InducedChunk chunk{{}, {}, d_nodes.p, n_steps, d_label.p, d_tables.p};
+        InducedChunk chunk{{}, {}, dg.d_nodes.p, dg.n_steps, dg.d_label.p, d_tables.p};
         for (size_t t = c0, f = 0; t < c1; ++t) {
             const uint64_t k = todo[t], a = pairs[2 * k], b = pairs[2 * k + 1];
             while (firsts[f] != a) ++f;
-            if (ids_bad(b)) continue;   // decided on the host (after the device's repeat check)
+            if (dg.ids_bad(b)) continue;   // decided on the host (after the device's repeat check)
             chunk.jobs.push_back(ClInducedJob{g->path_off[a], g->path_off[a + 1] - g->path_off[a], g->path_off[b], g->path_off[b + 1] - g->path_off[b],
                                               f * (table_bytes / sizeof(uint32_t)), 0, 0});
             chunk.job_pair.push_back(k);
@@ -451,13 +495,21 @@ int induced_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs
         if ((rc = pass(chunk))) return rc;
         std::vector<uint32_t> rep(firsts.size());
         HIP_TRY(ctx, cl_copy_sync(ctx, rep.data(), d_rep.p, rep.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t f = 0; f < firsts.size(); ++f) repeated[firsts[f]] |= rep[f] != 0;
+        for (size_t f = 0; f < firsts.size(); ++f) dg.repeated[firsts[f]] |= rep[f] != 0;
         c0 = c1;
     }
+    return CL_OK;
+}
+
+// The frame of cl_induced_pairwise_cigars, _stats, _profiles and cl_induced_gap_events_batch: the graph on the device, chunks of the pairs with
+// pass(chunk) for each, and at the end the code of the first failing pair (cl_induced_pairwise_cigar's order of checks).
+template <class Pass>
+int induced_batch(cl_context* ctx, const cl_base_graph* g, const uint64_t* pairs, uint64_t n_pairs, Pass&& pass) {
+    InducedGraph dg(ctx, g);
+    const int rc = induced_chunks(dg, pairs, n_pairs, pass);
+    if (rc) return rc;
     for (uint64_t k = 0; k < n_pairs; ++k) {   // the first failing pair decides
-        int e = pre[k];
-        if (e == CL_OK && repeated[pairs[2 * k]]) e = CL_ERR_CYCLIC_GRAPH;
-        if (e == CL_OK && ids_bad(pairs[2 * k + 1])) e = CL_ERR_INVALID_ARGUMENT;
+        const int e = dg.code(pairs[2 * k], pairs[2 * k + 1]);
         if (e != CL_OK) {
             cl_set_error(ctx, "induced pairwise alignment of paths %llu and %llu (pair %llu): %s", (unsigned long long)pairs[2 * k],
                          (unsigned long long)pairs[2 * k + 1], (unsigned long long)k, e == CL_ERR_CYCLIC_GRAPH ? "the first path follows a cycle" : "invalid path");
@@ -510,8 +562,8 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* g, const ui
     int rc = induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
         std::vector<ClInducedJob>& jobs = c.jobs;
         int rc;
-        DevBuf<ClInducedJob> d_jobs;
-        DevBuf<int64_t> d_len;
+        ScopedBuf<ClInducedJob> d_jobs;
+        ScopedBuf<int64_t> d_len;
         std::vector<int64_t> len(jobs.size());
         if ((rc = d_jobs.upload(ctx, jobs)) || (rc = d_len.alloc(ctx, jobs.size()))) return rc;
         HIP_TRY(ctx, cl_launch_induced_runs(false, d_jobs.p, (uint32_t)jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, d_len.p, nullptr, ctx->stream));
@@ -526,7 +578,7 @@ int cl_induced_pairwise_cigars(cl_context* ctx, const cl_base_graph* g, const ui
                 bytes += (uint64_t)len[w1];
                 ++w1;
             }
-            DevBuf<char> d_text;
+            ScopedBuf<char> d_text;
             std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
             std::vector<char> host(bytes);
             if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_text.alloc(ctx, bytes))) return rc;
@@ -554,8 +606,8 @@ int cl_induced_pairwise_stats(cl_context* ctx, const cl_base_graph* g, const uin
     if (!ctx || !g || (n_pairs && (!pairs || !out))) return CL_ERR_INVALID_ARGUMENT;
     return induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
         int rc;
-        DevBuf<ClInducedJob> d_jobs;
-        DevBuf<cl_pair_stats> d_stats;
+        ScopedBuf<ClInducedJob> d_jobs;
+        ScopedBuf<cl_pair_stats> d_stats;
         std::vector<cl_pair_stats> stats(c.jobs.size());
         if ((rc = d_jobs.upload(ctx, c.jobs)) || (rc = d_stats.alloc(ctx, c.jobs.size()))) return rc;
         HIP_TRY(ctx, cl_launch_induced_stats(d_jobs.p, (uint32_t)c.jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, d_stats.p, ctx->stream));
@@ -597,8 +649,8 @@ int cl_induced_pairwise_profiles(cl_context* ctx, const cl_base_graph* g, const 
                 n += jobs[w1].text_cap;
                 ++w1;
             }
-            DevBuf<ClInducedJob> d_jobs;
-            DevBuf<cl_pair_window> d_win;
+            ScopedBuf<ClInducedJob> d_jobs;
+            ScopedBuf<cl_pair_window> d_win;
             std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
             if (host.size() < n) host.resize(n);
             if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_win.alloc(ctx, n))) return rc;
@@ -626,8 +678,8 @@ int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* g, const u
     int rc = induced_batch(ctx, g, pairs, n_pairs, [&](InducedChunk& c) -> int {
         std::vector<ClInducedJob>& jobs = c.jobs;
         int rc;
-        DevBuf<ClInducedJob> d_jobs;
-        DevBuf<int64_t> d_cnt;
+        ScopedBuf<ClInducedJob> d_jobs;
+        ScopedBuf<int64_t> d_cnt;
         std::vector<int64_t> cnt(jobs.size());
         if ((rc = d_jobs.upload(ctx, jobs)) || (rc = d_cnt.alloc(ctx, jobs.size()))) return rc;
         HIP_TRY(ctx, cl_launch_induced_events(false, d_jobs.p, (uint32_t)jobs.size(), c.d_nodes, c.n_steps, c.d_label, g->n_nodes, c.d_tables, min_len, d_cnt.p, nullptr, ctx->stream));
@@ -643,7 +695,7 @@ int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* g, const u
                 ++w1;
             }
             if (n) {
-                DevBuf<cl_gap_event> d_ev;
+                ScopedBuf<cl_gap_event> d_ev;
                 std::vector<ClInducedJob> sub(jobs.begin() + w0, jobs.begin() + w1);
                 if (host.size() < n) host.resize(n);
                 if ((rc = d_jobs.upload(ctx, sub)) || (rc = d_ev.alloc(ctx, n))) return rc;
@@ -663,6 +715,88 @@ int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* g, const u
     if (!ev) return CL_ERR_OUT_OF_MEMORY;
     for (uint64_t k = 0; k < n_pairs; ++k) if (!events[k].empty()) memcpy(ev + offsets_out[k], events[k].data(), events[k].size() * sizeof(cl_gap_event));
     *out = ev;
+    return CL_OK;
+}
+
+int cl_induced_pairwise_agreements(cl_context* ctx, const cl_base_graph* a, const cl_base_graph* b, const uint64_t* quads, uint64_t n, cl_pair_agreement* out) {
+    cl_bind_device(ctx);
+    if (!ctx || !a || !b || (n && (!quads || !out))) return CL_ERR_INVALID_ARGUMENT;
+    InducedGraph da(ctx, a), db(ctx, b);
+    auto len = [](const cl_base_graph* g, uint64_t p) { return g->path_off[p + 1] - g->path_off[p]; };
+    // what needs no device: a path index out of range in either graph, lengths that differ, a path 1 whose indices do not fit a partner word.  Such
+    // a quad is left out of both passes; its code is decided at the end, behind what the device finds (a first, then b, then the lengths)
+    auto host_refuses = [&](const uint64_t* q) {
+        if (q[0] >= a->n_paths || q[1] >= a->n_paths || q[2] >= b->n_paths || q[3] >= b->n_paths) return true;
+        return len(a, q[0]) != len(b, q[2]) || len(a, q[1]) != len(b, q[3]) || len(a, q[0]) >= 0x7FFFFFFFull;
+    };
+    std::vector<cl_pair_agreement> host;
+    for (uint64_t g0 = 0; g0 < n;) {
+        // one group: quads in order whose partner slices fit in kChunkPartnerBytes (at least one quad); slot = the quad's place in the group
+        std::vector<uint64_t> pairs_a, pairs_b, slice, quad_of;
+        uint64_t words = 0, g1 = g0;
+        for (; g1 < n; ++g1) {
+            const uint64_t* q = quads + 4 * g1;
+            if (host_refuses(q)) continue;
+            const uint64_t n2 = len(a, q[1]);
+            if (!quad_of.empty() && (words + n2) * sizeof(uint32_t) > kChunkPartnerBytes) break;
+            pairs_a.insert(pairs_a.end(), {q[0], q[1]});
+            pairs_b.insert(pairs_b.end(), {q[2], q[3]});
+            slice.push_back(words);
+            quad_of.push_back(g1);
+            words += n2;
+        }
+        const uint64_t slots = quad_of.size();
+        if (slots) {
+            int rc;
+            ScopedBuf<uint32_t> d_partner;
+            ScopedBuf<uint64_t> d_counts;
+            ScopedBuf<cl_pair_agreement> d_out;
+            if ((rc = d_partner.alloc(ctx, words)) || (rc = d_counts.alloc(ctx, 2 * slots)) || (rc = d_out.alloc(ctx, slots))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(d_partner.p, 0xFF, std::max<uint64_t>(words, 1) * sizeof(uint32_t), ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_counts.p, 0, 2 * slots * sizeof(uint64_t), ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_out.p, 0, slots * sizeof(cl_pair_agreement), ctx->stream));
+            // both passes find a pair's slice and slot through job_pair: a and b order and chunk the pairs each in their own way
+            auto place = [&](InducedChunk& c) {
+                for (size_t j = 0; j < c.jobs.size(); ++j) { c.jobs[j].text_off = slice[c.job_pair[j]]; c.jobs[j].text_cap = c.job_pair[j]; }
+            };
+            rc = induced_chunks(da, pairs_a.data(), slots, [&](InducedChunk& c) -> int {
+                int rc;
+                ScopedBuf<ClInducedJob> d_jobs;
+                place(c);
+                if ((rc = d_jobs.upload(ctx, c.jobs))) return rc;
+                HIP_TRY(ctx, cl_launch_induced_partner(d_jobs.p, (uint32_t)c.jobs.size(), c.d_nodes, c.n_steps, c.d_label, a->n_nodes, c.d_tables, d_partner.p, d_counts.p, ctx->stream));
+                return CL_OK;
+            });
+            if (rc) return rc;
+            rc = induced_chunks(db, pairs_b.data(), slots, [&](InducedChunk& c) -> int {
+                int rc;
+                ScopedBuf<ClInducedJob> d_jobs;
+                place(c);
+                if ((rc = d_jobs.upload(ctx, c.jobs))) return rc;
+                HIP_TRY(ctx, cl_launch_induced_agreement(d_jobs.p, (uint32_t)c.jobs.size(), c.d_nodes, c.n_steps, c.d_label, b->n_nodes, c.d_tables, d_partner.p, d_counts.p, d_out.p,
+                                                         ctx->stream));
+                return CL_OK;
+            });
+            if (rc) return rc;
+            host.resize(slots);
+            HIP_TRY(ctx, cl_copy_sync(ctx, host.data(), d_out.p, slots * sizeof(cl_pair_agreement), hipMemcpyDeviceToHost));
+            for (uint64_t j = 0; j < slots; ++j) out[quad_of[j]] = host[j];
+        }
+        g0 = g1;
+    }
+    for (uint64_t k = 0; k < n; ++k) {   // the first failing quad decides: a's code, then b's, then the lengths
+        const uint64_t* q = quads + 4 * k;
+        if (host_refuses(q)) { da.find_repeats(q[0]); db.find_repeats(q[2]); }   // (no pass saw this quad)
+        int e = da.code(q[0], q[1]);
+        if (e == CL_OK) e = db.code(q[2], q[3]);
+        if (e == CL_OK && host_refuses(q)) e = CL_ERR_INVALID_ARGUMENT;
+        if (e != CL_OK) {
+            cl_set_error(ctx, "agreement of paths %llu and %llu with paths %llu and %llu (quad %llu): %s", (unsigned long long)q[0], (unsigned long long)q[1],
+                         (unsigned long long)q[2], (unsigned long long)q[3], (unsigned long long)k,
+                         e == CL_ERR_CYCLIC_GRAPH ? "the first path follows a cycle" : "invalid path, or the two graphs' paths differ in length");
+            return e;
+        }
+    }
     return CL_OK;
 }
 

@@ -377,6 +377,13 @@ hipError_t cl_launch_induced_profile(const ClInducedJob* jobs, uint32_t n_jobs, 
                                      const uint32_t* tables, uint64_t window, cl_pair_window* windows, hipStream_t stream);
 hipError_t cl_launch_induced_events(bool write, const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label,
                                     uint64_t n_nodes, const uint32_t* tables, uint64_t min_len, int64_t* n_events, cl_gap_event* events, hipStream_t stream);
+// the agreement of two graphs' alignments (cl_induced_pairwise_agreements).  text_off: the first word of the pair's slice of `partner` (n2 words, preset
+// to 0xFFFFFFFF), text_cap: the pair's slot in `counts` (two words a slot) and `out`.  The partner pass runs on graph a's paths, labels and tables
+// and fills slices and counts; the agreement pass runs on graph b's, behind it on the same stream, and writes out[slot]
+hipError_t cl_launch_induced_partner(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                     const uint32_t* tables, uint32_t* partner, uint64_t* counts, hipStream_t stream);
+hipError_t cl_launch_induced_agreement(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                       const uint32_t* tables, const uint32_t* partner, const uint64_t* counts, cl_pair_agreement* out, hipStream_t stream);
 
 // subaln_kernels.hip: the -s lines of one merge (cl_subaln_api.cpp).  One side of the merge on the device: the per-node step table
 // ((path << 32) | step of the node's first occurrence, UINT64_MAX: on no path), the labels, and the path names back to back

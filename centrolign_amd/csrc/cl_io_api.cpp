@@ -445,4 +445,38 @@ int cl_induced_gap_events(const cl_base_graph* g, uint64_t path1, uint64_t path2
     return CL_OK;
 }
 
+// two graphs' alignments of the same two sequences compared (header): a's aligned pairs as a map i2 -> i1, b's looked up in it
+int cl_induced_pairwise_agreement(const cl_base_graph* a, uint64_t a1, uint64_t a2, const cl_base_graph* b, uint64_t b1, uint64_t b2, cl_pair_agreement* out) {
+    if (!out) return CL_ERR_INVALID_ARGUMENT;
+    InducedAln aln_a, aln_b;
+    int rc = induced_pairwise_alignment(a, a1, a2, aln_a);
+    if (rc) return rc;
+    if ((rc = induced_pairwise_alignment(b, b1, b2, aln_b))) return rc;
+    const uint64_t n1 = a->path_off[a1 + 1] - a->path_off[a1], n2 = a->path_off[a2 + 1] - a->path_off[a2];
+    if (n1 != b->path_off[b1 + 1] - b->path_off[b1] || n2 != b->path_off[b2 + 1] - b->path_off[b2] || n1 >= 0x7FFFFFFFull) return CL_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    out->n1 = n1;
+    out->n2 = n2;
+    constexpr uint32_t none = 0xFFFFFFFFu, eq_bit = 0x80000000u;   // the device's partner word
+    std::vector<uint32_t> partner(n2, none);
+    for (const auto& ap : aln_a) {
+        if (ap.first == kNoStep || ap.second == kNoStep) continue;
+        const bool eq = induced_op(a, a1, a2, ap) == '=';
+        ++out->aligned_a;
+        out->eq_a += eq;
+        if (ap.first < n1) partner[ap.second] = (uint32_t)ap.first | (eq ? eq_bit : 0u);
+    }
+    for (const auto& ap : aln_b) {
+        if (ap.first == kNoStep || ap.second == kNoStep) continue;
+        ++out->aligned_b;
+        out->eq_b += induced_op(b, b1, b2, ap) == '=';
+        if (ap.first >= n1) continue;
+        const uint32_t w = partner[ap.second];
+        if (w == none || (w & ~eq_bit) != (uint32_t)ap.first) continue;
+        ++out->shared;
+        out->shared_eq += (w & eq_bit) != 0;
+    }
+    return CL_OK;
+}
+
 }  // extern "C"

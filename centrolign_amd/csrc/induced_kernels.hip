@@ -29,6 +29,12 @@
 // (e_prev + 1, last + 1), its D token has length e - e_prev - 1, its I token stands at (e, last + 1) and the match at (e, s).  So neither needs a
 // positional scan.  The profile adds every token to the bins of the path-1 windows it covers (integer atomics, reduced per wave first: the result
 // does not depend on scheduling); the events kernel counts, then writes, the I and D tokens of at least min_len bases, each of which is one run.
+//
+// cl_induced_pairwise_agreements compares the alignments two graphs `a` and `b` imply for the same pair of sequences.  The i2 of a CIGAR's '=' / 'X'
+// columns strictly increases, so a graph's aligned pairs are a partial map i2 -> i1: induced_partner_kernel walks the tokens of `a` and stores
+// that map, one 32-bit word per step of path 2 (the pair's slice of a scratch buffer preset to kNoPos; bit 31: the column is '=' in `a`), and
+// induced_agreement_kernel walks the tokens of `b` on the same stream and counts the columns whose word holds their own i1.  Both follow from
+// scan 1 alone, like the profile; all sums are integer workgroup sums.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -607,6 +613,122 @@ __global__ void __launch_bounds__(kThreads) induced_events_kernel(const ClInduce
     if (!kWrite) n_events[blockIdx.x] = carry;
 }
 
+// ------------------------------------------------------------ agreement of two graphs ---------------------------------------------------------
+// A partner word: the path-1 index a graph aligns a step of path 2 with, bit 31 set where the column is '='; kNoPos: the step is not aligned.
+// Path 1 has fewer than 2^31 - 1 steps (the host checks), so no word of an aligned step equals kNoPos.
+constexpr uint32_t kPartnerEq = 0x80000000u;
+
+struct SumScan4 {
+    uint64_t v[4];
+    __device__ SumScan4 down(unsigned d) const {
+        SumScan4 o;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) o.v[k] = (uint64_t)__shfl_down((long long)v[k], d, 64);
+        return o;
+    }
+};
+// the workgroup's sums, in thread 0 alone; lds: kWaves entries
+__device__ __forceinline__ SumScan4 block_sum4(SumScan4 s, SumScan4* lds) {
+    const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (unsigned d = 32; d >= 1; d >>= 1) {
+        const SumScan4 o = s.down(d);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) s.v[k] += o.v[k];   // (lanes whose partner lies past the wave add a value nobody reads: lane 0's sum is exact)
+    }
+    if (lane == 0) lds[w] = s;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (unsigned i = 1; i < kWaves; ++i)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) s.v[k] += lds[i].v[k];
+    return s;
+}
+
+// Scan 1 as in induced_stats_kernel; every '=' / 'X' token (i1, i2) is counted, and — kStore: graph `a` — stored as partner[i2] where i1 lies on
+// path 1, or — !kStore: graph `b` — compared with partner[i2].  A token of a short equal gap run belongs to a step before the thread's own, in
+// the previous tile when the thread is a tile's first, and the run after the last match is thread 0's: every store and every load is guarded by
+// i2 < n2, the length of the pair's slice.  job.text_off: the slice's first word in `partner`; job.text_cap: the pair's slot in `counts` / `out`.
+// kStore: counts[slot] = {aligned_a, eq_a}.  !kStore: out[slot], all 64 bytes, once.
+template <bool kStore>
+__device__ __forceinline__ void partner_agreement_walk(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                       const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                       uint32_t* partner_words, uint64_t* counts, cl_pair_agreement* out) {
+    __shared__ MatchScan lds1[kWaves];
+    __shared__ SumScan4 lds2[kWaves];
+    const ClInducedJob job = jobs[blockIdx.x];
+    const uint32_t* pos = tables + job.table;
+    PairView v{path_nodes + job.off1, path_nodes + job.off2, path_nodes + n_steps, label, n_nodes, (int64_t)job.n1, (int64_t)job.n2};
+    uint32_t* partner = partner_words + job.text_off;
+    SumScan4 sum{{0, 0, 0, 0}};   // aligned, eq, shared, shared_eq
+    auto tok = [&](uint32_t op, int64_t, int64_t i1, int64_t i2) {
+        if (op > kOpX) return;   // D, I
+        sum.v[0] += 1;
+        sum.v[1] += op == kOpEq;
+        if (i1 < 0 || i1 >= v.n1 || i2 < 0 || i2 >= v.n2) return;   // past path 1: aligned, never shared; i2: the slice's bound
+        if (kStore) {
+            partner[i2] = (uint32_t)i1 | (op == kOpEq ? kPartnerEq : 0u);
+        } else {
+            const uint32_t w = partner[i2];
+            const bool same = w != kNoPos && (w & ~kPartnerEq) == (uint32_t)i1;
+            sum.v[2] += same;
+            sum.v[3] += same && (w & kPartnerEq);
+        }
+    };
+    MatchScan c1 = MatchScan::ident();
+    for (int64_t base = 0; base < v.n2; base += kTile) {
+        const int64_t s0 = base + (int64_t)threadIdx.x * kItems;
+        uint32_t a[kItems];
+        MatchScan agg = MatchScan::ident();
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            a[r] = kNoPos;
+            if (s0 + r < v.n2) a[r] = pos[v.p2[s0 + r]];
+            if (a[r] != kNoPos) agg = combine(agg, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+        MatchScan tot1;
+        MatchScan x = combine(c1, block_exclusive(agg, lds1, tot1));
+        c1 = combine(c1, tot1);
+#pragma unroll
+        for (uint32_t r = 0; r < kItems; ++r) {
+            if (a[r] == kNoPos) continue;
+            match_tokens_at(v, x, s0 + r, (int64_t)a[r], tok);
+            x = combine(x, MatchScan{1, s0 + r, (int64_t)a[r]});
+        }
+    }
+    if (threadIdx.x == 0) {
+        // the run after the last match, as in induced_runs_kernel
+        const int64_t k = c1.cnt;
+        const int64_t e_last = k > 0 ? k - 1 + (c1.best > 0 ? c1.best : 0) : -1;
+        const int64_t g2 = v.n1 > e_last + 1 ? v.n1 - e_last - 1 : 0, g1 = v.n2 - 1 - c1.last;
+        gap_run_tokens_at(v, e_last, c1.last, g1, g2, tok);
+    }
+    sum = block_sum4(sum, lds2);
+    if (threadIdx.x != 0) return;
+    uint64_t* mine = counts + 2 * job.text_cap;
+    if (kStore) {
+        mine[0] = sum.v[0];
+        mine[1] = sum.v[1];
+    } else {
+        cl_pair_agreement r;
+        r.aligned_a = mine[0]; r.aligned_b = sum.v[0]; r.shared = sum.v[2];
+        r.eq_a = mine[1]; r.eq_b = sum.v[1]; r.shared_eq = sum.v[3];
+        r.n1 = job.n1; r.n2 = job.n2;
+        out[job.text_cap] = r;
+    }
+}
+__global__ void __launch_bounds__(kThreads) induced_partner_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                                  const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                                  uint32_t* __restrict__ partner, uint64_t* __restrict__ counts) {
+    partner_agreement_walk<true>(jobs, path_nodes, n_steps, label, n_nodes, tables, partner, counts, nullptr);
+}
+__global__ void __launch_bounds__(kThreads) induced_agreement_kernel(const ClInducedJob* __restrict__ jobs, const uint32_t* __restrict__ path_nodes, uint64_t n_steps,
+                                                                    const uint8_t* __restrict__ label, uint64_t n_nodes, const uint32_t* __restrict__ tables,
+                                                                    const uint32_t* __restrict__ partner, const uint64_t* __restrict__ counts,
+                                                                    cl_pair_agreement* __restrict__ out) {
+    partner_agreement_walk<false>(jobs, path_nodes, n_steps, label, n_nodes, tables, const_cast<uint32_t*>(partner), const_cast<uint64_t*>(counts), out);
+}
+
 // pos[path1[i]] = i; a node met twice leaves one of its positions behind, which the check reads back
 __global__ void induced_scatter_kernel(const uint32_t* __restrict__ p1, uint64_t n1, uint32_t* __restrict__ pos) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * blockDim.x) pos[p1[i]] = (uint32_t)i;
@@ -654,5 +776,19 @@ hipError_t cl_launch_induced_events(bool write, const ClInducedJob* jobs, uint32
     if (n_jobs == 0) return hipSuccess;
     if (write) hipLaunchKernelGGL(induced_events_kernel<true>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, min_len, n_events, events);
     else hipLaunchKernelGGL(induced_events_kernel<false>, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, min_len, n_events, events);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_partner(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                     const uint32_t* tables, uint32_t* partner, uint64_t* counts, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(induced_partner_kernel, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, partner, counts);
+    return hipGetLastError();
+}
+
+hipError_t cl_launch_induced_agreement(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
+                                       const uint32_t* tables, const uint32_t* partner, const uint64_t* counts, cl_pair_agreement* out, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(induced_agreement_kernel, dim3(n_jobs), dim3(kThreads), 0, stream, jobs, path_nodes, n_steps, label, n_nodes, tables, partner, counts, out);
     return hipGetLastError();
 }

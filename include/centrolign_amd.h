@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 17   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 18   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -682,6 +682,29 @@ int cl_induced_pairwise_profiles(cl_context* ctx, const cl_base_graph* graph, co
                                  uint64_t* offsets_out /* [n_pairs + 1] */);
 int cl_induced_gap_events_batch(cl_context* ctx, const cl_base_graph* graph, const uint64_t* pairs, uint64_t n_pairs, uint64_t min_len, cl_gap_event** out,
                                 uint64_t* offsets_out /* [n_pairs + 1] */);
+/* The agreement of two graphs on one pair of sequences: the sum-of-pairs measure.  Graphs a and b hold the same sequences; path a1 of a and b1 of b
+ * are one sequence (path 1), a2 and b2 another (path 2), in the same orientation.  Read cl_induced_pairwise_cigar(graph, path1, path2) left to right
+ * with i1 = i2 = 0 as above: every '=' or 'X' column is an aligned pair (i1, i2).  S_g is the set of graph g's aligned pairs with i1 < n1 (n1:
+ * the steps of path 1); the columns whose i1 runs past path 1 (path 2 meeting path 1's nodes out of order or twice) count as aligned but are
+ * never shared.  shared = |S_a n S_b|; shared / aligned_a and shared / aligned_b are recall and precision of b against a.  shared_eq counts the
+ * shared pairs that are '=' by a's labels.  In a CIGAR the i2 of the aligned pairs strictly increases, so a graph aligns a step of path 2 at
+ * most once.
+ * cl_induced_pairwise_agreement: host only, the definition.  cl_induced_pairwise_agreements: every quad (a1, a2, b1, b2) in two device passes
+ * (induced_kernels.hip: a's aligned pairs go into one 32-bit word per step of path 2 — bit 31: '=' in a —, b's are compared with them; no
+ * text; 64 bytes per quad come back).  Path indices may differ between the graphs; quads may repeat; n == 0 is allowed.  Error codes: those of
+ * cl_induced_pairwise_stats for (a, a1, a2), then for (b, b1, b2), then CL_ERR_INVALID_ARGUMENT where the lengths of a1 and b1 or of a2 and b2
+ * differ, or where path 1 has 2^31 - 1 steps or more (its indices share a word with the '=' bit); the first failing quad decides (out is then
+ * unspecified).  Lengths only: that the bases agree is the caller's check.  Device memory beyond both graphs' paths and labels: at most 256 MB
+ * of position tables and 256 MB of partner words (or one quad's) at a time. */
+typedef struct cl_pair_agreement {
+    uint64_t aligned_a, aligned_b;   /* '=' + 'X' columns of each graph's CIGAR: cl_pair_stats eq + x */
+    uint64_t shared;                 /* |S_a n S_b| */
+    uint64_t eq_a, eq_b, shared_eq;  /* the '=' columns among them; shared_eq judged by a's labels */
+    uint64_t n1, n2;                 /* path lengths */
+} cl_pair_agreement;                 /* 64 bytes */
+int cl_induced_pairwise_agreement(const cl_base_graph* a, uint64_t a1, uint64_t a2, const cl_base_graph* b, uint64_t b1, uint64_t b2, cl_pair_agreement* out);
+int cl_induced_pairwise_agreements(cl_context* ctx, const cl_base_graph* a, const cl_base_graph* b, const uint64_t* quads /* [4 * n]: a1, a2, b1, b2 */, uint64_t n,
+                                   cl_pair_agreement* out /* [n] */);
 /* The -A output of the CLI after cyclisation (src/core.cpp:537-545): output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), graph,
  * path1, path2) (src/alignment.cpp:569-904) — blocks of colinear alignment between the two paths of a graph that may have cycles; name1 / name2
  * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
