@@ -1,4 +1,4 @@
-// chain_device.h — device-side layout of a packed chaining problem (shared by cl_chain_api.cpp and chain_kernels.hip)
+// chain_device.h — device-side layout of a packed chaining problem (shared by cl_chain_device.cpp and chain_kernels.hip)
 #ifndef CL_CHAIN_DEVICE_H
 #define CL_CHAIN_DEVICE_H
 
@@ -84,7 +84,7 @@ constexpr int kFarLeafShift = 6;
 constexpr int kFarFanShift = 3;
 constexpr int kFarMaxLevels = 4;     // up to 32768 records: one wave seals a node in about a millisecond
 constexpr uint32_t kFarLag = 8;       // upper limit of the far pass's lag: the far pass of macro-block k reads the records final `lag`
-                                      // macro-blocks earlier, so that many far launches run side by side (cl_chain_api.cpp picks the lag)
+                                      // macro-blocks earlier, so that many far launches run side by side (cl_chain_device.cpp picks the lag)
 constexpr int kFarBandShift = 16;   // shift buckets of 65536 by default (ClFarDevice::band_shift; wider when the shifts span more than 2^15 buckets): beyond
                                     // that the gap cost is on its last, nearly flat piece.  Measured on 2 x 1 Mbp: buckets of 4096 / 1024 / 256 open 3.4x /
                                     // 3.6x / 3.7x the leaves (the "everything else pays one bucket width" term gets weak), 572 / 751 / 812 ms against 366

@@ -16,7 +16,7 @@
 // three roundings of magnitudes below |dp| + scale * extend_0 * (|shift| + |q|) + scale * open_max + |w| are covered by the
 // allowance  2^-21 x that magnitude  added to the bound.  A node whose bound is STRICTLY below the query's best candidate so
 // far cannot hold a record that attains the query's final DP value in any tree kind, so skipping it changes neither the DP
-// value nor any running maximum the traceback will read for an attaining kind (cl_chain_api.cpp); nodes that survive are
+// value nor any running maximum the traceback will read for an attaining kind (cl_chain_traceback.cpp); nodes that survive are
 // opened level by level, and surviving leaves are evaluated record by record with the exact arithmetic of the sweep.
 //
 // Eight lanes work on one query: a round tests eight sibling nodes (one per lane), surviving leaves are scanned by the eight
@@ -625,7 +625,7 @@ __global__ void __launch_bounds__(256) far_prune_kernel(ClChainDevice D, ClFarDe
         }
         sp += __popcll(mask);
     }
-    // bookkeeping for the host's choice between this pass and the all-pairs sweep (cl_chain_api.cpp): leaves this query scanned
+    // bookkeeping for the host's choice between this pass and the all-pairs sweep (cl_chain_device.cpp: enqueue_walk): leaves this query scanned
     // against the leaves it had in range.  A scanned leaf costs about what sixteen leaves cost the sweep (divergent loads
     // instead of LDS broadcasts, plus the tests that led to it).
     {

@@ -18,7 +18,7 @@
 //                        the pairs after it.
 // O(M^2/2) pair evaluations instead of O(M log^2 M) tree steps, but all of them independent: 922 k pairs
 // (the 2 x 1 Mbp config) are 4.3e11 evaluations.  Which predecessor the reference's trees would report among
-// EQUAL maxima is decided afterwards on the host, only for the pairs on the optimal chain (cl_chain_api.cpp).
+// EQUAL maxima is decided afterwards on the host, only for the pairs on the optimal chain (cl_chain_traceback.cpp).
 //
 // Compiled with -ffp-contract=off: the candidate values must round exactly like the reference's scalar code.
 #include <hip/hip_runtime.h>
@@ -838,13 +838,13 @@ hipError_t cl_chain_launch_own_rec(const ClChainDevice& D, uint32_t max_recs, hi
 }
 
 // the query results of ONE pair in every combination (7 per combination), for a traceback that fetches rows as it goes instead of downloading
-// 28 bytes x pairs x combinations (cl_chain_api.cpp)
+// 28 bytes x pairs x combinations (cl_chain_device.cpp)
 __global__ void __launch_bounds__(256) chain_acc_row_kernel(const ClChainCombo* combos, uint32_t n_combos, uint32_t s, int* out) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_combos * 7) out[i] = combos[i / 7].acc[(size_t)s * 7 + i % 7];
 }
 
-// the dense query tables out of their factors (cl_chain_api.cpp: factored queries): combination c = (tag1, tag2); fa_d == nullptr: the gap-free DP (no shifts)
+// the dense query tables out of their factors (cl_chain_prep.cpp: factored queries): combination c = (tag1, tag2); fa_d == nullptr: the gap-free DP (no shifts)
 __global__ void __launch_bounds__(256) chain_expand_queries_kernel(const uint32_t* fa_qt, const uint32_t* fa_d, const uint32_t* fb_qoff, const uint32_t* fb_d,
                                                                    const uint32_t* combo_tags, uint32_t n_pairs, uint32_t* qt, uint32_t* qoff, int32_t* q, uint32_t combo_base) {
     const uint32_t c = combo_base + blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;

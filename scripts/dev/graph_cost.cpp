@@ -1,5 +1,5 @@
 // What would a hipGraph of the chaining DP's macro-block loop cost?  ("measure a hipGraph per 64-128 macro-blocks before declining it again".)
-// The loop of chain_dp_batch (cl_chain_api.cpp) per macro-block k: far(k) on a side stream behind seal(k - lag - 1); near(k), walk(k) on the serial stream, walk behind
+// The loop of chain_dp_batch (cl_chain_device.cpp: enqueue_walk) per macro-block k: far(k) on a side stream behind seal(k - lag - 1); near(k), walk(k) on the serial stream, walk behind
 // far(k); seal(k) on the sealing stream behind walk(k): four launches, three cross-stream edges.  This program builds exactly that dependency pattern out of empty
 // kernels (plus a ~20 us spin kernel for "walk", so that the device side is a chain as in the DP) and times, for B macro-blocks:
 //   (a) direct enqueue (hipExtLaunchKernel with stop events + hipStreamWaitEvent, as the library does): host time to enqueue, time until the device is done;

@@ -454,7 +454,7 @@ def sweep_result_diff(res, z, prefix, check_score, check_choice):
 
 # the chaining DP across the number of chain combinations ---------------------------------------------------------------
 # (tests/test_combo_sweep.py, tests/test_gpu_combo_sweep.py, tests/golden/make_combo_sweep.py)
-# paths of graph 1 x paths of graph 2 on both sides of every count at which cl_chain_api.cpp changes its device path: 1 | 2 (the one-combination
+# paths of graph 1 x paths of graph 2 on both sides of every count at which cl_chain_device.cpp (choose_path) changes its device path: 1 | 2 (the one-combination
 # specialisations), 8 | 9 (chain_walk2), 16 | 17 (granules | atomic maximum + arrival count), 256 | 257, 512 | 513, 768 | 770 (one, two, three combinations
 # per walk workgroup, then the group-by-group path), 4 096 | 4 160 tags (parallel | serial numbering), 65 535 | 65 536 (a launch dimension's limit)
 COMBO_PATHS = ((1, 1), (1, 2), (2, 2), (2, 4), (3, 3), (4, 4), (1, 17), (2, 9), (16, 16), (1, 257), (16, 32), (19, 27), (24, 32), (22, 35), (32, 33),

@@ -1,4 +1,4 @@
-"""GPU suite: the sparse affine chaining DP across the number of chain combinations of a merge (pairs of paths that share a match pair).  cl_chain_api.cpp
+"""GPU suite: the sparse affine chaining DP across the number of chain combinations of a merge (pairs of paths that share a match pair).  cl_chain_device.cpp
 changes its device path with that number — the one-combination specialisations, chain_walk2 up to 8, granules up to 16 and one atomic maximum + arrival count
 per pair beyond, one / two / three combinations per walk workgroup up to 256 / 512 / 768, the group-by-group kernels beyond, parallel or serial numbering of the
 combinations around 4 096 tags, several launches where a combination index is a launch dimension beyond 65 535 — and tests/helpers.py:combo_cases() has an

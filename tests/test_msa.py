@@ -180,7 +180,7 @@ def test_gpu_worker_contexts_on_a_list_of_devices(gpu_ctx):
 @pytest.mark.parametrize("case", list(WIDE))
 def test_gpu_wide_merges(gpu_ctx, case):
     """sequences over a balanced tree whose root merge pairs 12 + 12 paths = 144 chain combinations (the walk kernel with its reduction exchange,
-    cl_chain_api.cpp) and 25 + 25 paths = 625 (beyond the walk kernel's 256: the per-block kernels) — BASELINE configs[4]'s width at small
+    cl_chain_device.cpp) and 25 + 25 paths = 625 (beyond the walk kernel's 256: the per-block kernels) — BASELINE configs[4]'s width at small
     length.  The GFA is the one the unmodified reference printed (tests/golden/make_wide_merge.py: 26 and 34 CPU-minutes there), byte for
     byte; the narrower case also with one worker"""
     import gzip
