@@ -561,6 +561,115 @@ def induced_pairwise_agreements(graph_a, graph_b, quads, ctx):
     return out
 
 
+MSA_COLUMN_FIELDS = ("A", "C", "G", "T", "N", "gaps", "consensus", "flags")   # cl_msa_column, in the struct's order (32 bytes)
+MSA_LAYOUTS = {"level": 0, "node": 1}
+MSA_WANT_ROWS, MSA_WANT_COLUMNS, MSA_WANT_SITES = 1, 2, 4   # the bits of cl_msa_columns_params.want
+NO_COLUMN = 0xFFFFFFFF   # node_col of a node on no path
+
+
+class MsaColumnsParams(C.Structure):
+    """cl_msa_columns_params"""
+    _fields_ = [("layout", C.c_int32), ("want", C.c_uint32), ("min_minor", C.c_uint32), ("max_gaps", C.c_uint32), ("block_cols", C.c_uint64)]
+
+
+class MsaColumnsC(C.Structure):
+    """cl_msa_columns"""
+    _fields_ = [("n_paths", C.c_uint64), ("n_cols", C.c_uint64), ("n_sites", C.c_uint64), ("node_col", C.c_void_p), ("rows", C.c_void_p),
+                ("columns", C.c_void_p), ("site_col", C.c_void_p), ("site_rows", C.c_void_p)]
+
+
+def _layout_code(layout):
+    return MSA_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+def msa_column_layout(graph, layout="level"):
+    """cl_msa_column_layout (host only): (node_col — the column of every node, NO_COLUMN for a node on no path —, n_cols) under layout "level"
+    (0: the column is the node's level over the path edges) or "node" (1: one node per column, ordered by (level, node id))"""
+    lib = load_library()
+    g, col, n = graph.as_c(), np.zeros(max(len(graph.label), 1), np.uint32), C.c_uint64(0)
+    lib.cl_msa_column_layout.restype = C.c_int
+    lib.cl_msa_column_layout.argtypes = [C.POINTER(BaseGraphC), C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    rc = lib.cl_msa_column_layout(C.byref(g), _layout_code(layout), col.ctypes.data, C.byref(n))
+    if rc != 0:
+        raise ClError(rc, "cl_msa_column_layout")
+    return col[:len(graph.label)], int(n.value)
+
+
+def _msa_columns_params(lib, layout, want, min_minor, max_gaps, block_cols):
+    p = MsaColumnsParams()
+    lib.cl_msa_columns_params_default.restype = None
+    lib.cl_msa_columns_params_default.argtypes = [C.POINTER(MsaColumnsParams)]
+    lib.cl_msa_columns_params_default(C.byref(p))
+    if layout is not None:
+        p.layout = _layout_code(layout)
+    if want is not None:
+        p.want = int(want)
+    if min_minor is not None:
+        p.min_minor = int(min_minor)
+    if max_gaps is not None:
+        p.max_gaps = int(max_gaps)
+    if block_cols is not None:
+        p.block_cols = int(block_cols)
+    return p
+
+
+def _take_msa_columns(lib, out, n_nodes):
+    """the arrays of a cl_msa_columns as numpy copies (None for one that was not wanted), and the struct released"""
+    def arr(ptr, n, dtype, shape):
+        if not ptr:
+            return None
+        nbytes = int(n) * np.dtype(dtype).itemsize
+        raw = (C.c_char * nbytes).from_address(ptr) if nbytes else b""
+        return np.frombuffer(raw, dtype).reshape(shape).copy()
+    try:
+        P, W, S = int(out.n_paths), int(out.n_cols), int(out.n_sites)
+        return {"n_paths": P, "n_cols": W, "n_sites": S,
+                "node_col": arr(out.node_col, n_nodes, np.uint32, (n_nodes,)),
+                "rows": arr(out.rows, P * W, "S1", (P, W)),
+                "columns": arr(out.columns, 8 * W, np.uint32, (W, 8)),
+                "site_col": arr(out.site_col, S, np.uint64, (S,)),
+                "site_rows": arr(out.site_rows, P * S, "S1", (P, S))}
+    finally:
+        lib.cl_msa_columns_free.restype = None
+        lib.cl_msa_columns_free.argtypes = [C.POINTER(MsaColumnsC)]
+        lib.cl_msa_columns_free(C.byref(out))
+
+
+def msa_columns_layout_seconds():
+    """cl_msa_columns_layout_seconds: the wall time of the level pass inside this thread's last msa_columns_host or msa_columns call"""
+    lib = load_library()
+    lib.cl_msa_columns_layout_seconds.restype = C.c_double
+    lib.cl_msa_columns_layout_seconds.argtypes = []
+    return float(lib.cl_msa_columns_layout_seconds())
+
+
+def msa_columns_host(graph, layout=None, want=None, min_minor=None, max_gaps=None, block_cols=None):
+    """cl_msa_columns_host (host only, the definition): the MSA as columns.  A dict with n_paths, n_cols, n_sites, node_col, rows — an
+    (n_paths, n_cols) S1 array, '-' where a path has no base —, columns — an (n_cols, 8) uint32 array with MSA_COLUMN_FIELDS as columns —,
+    site_col and site_rows (n_paths, n_sites).  want: a sum of the MSA_WANT_* bits; an array that is not wanted is None.  Parameters left None keep cl_msa_columns_params_default's values (level, everything, min_minor 1, no limit on gaps)."""
+    lib = load_library()
+    g, out = graph.as_c(), MsaColumnsC()
+    p = _msa_columns_params(lib, layout, want, min_minor, max_gaps, block_cols)
+    lib.cl_msa_columns_host.restype = C.c_int
+    lib.cl_msa_columns_host.argtypes = [C.POINTER(BaseGraphC), C.POINTER(MsaColumnsParams), C.POINTER(MsaColumnsC)]
+    rc = lib.cl_msa_columns_host(C.byref(g), C.byref(p), C.byref(out))
+    if rc != 0:
+        raise ClError(rc, "cl_msa_columns_host")
+    return _take_msa_columns(lib, out, len(graph.label))
+
+
+def msa_columns(graph, ctx, layout=None, want=None, min_minor=None, max_gaps=None, block_cols=None):
+    """cl_msa_columns_compute: msa_columns_host's results from a device tile of block_cols columns at a time (0 / None: the default block) on
+    Context ctx; the same dict, byte for byte, whatever block_cols is"""
+    lib = load_library()
+    g, out = graph.as_c(), MsaColumnsC()
+    p = _msa_columns_params(lib, layout, want, min_minor, max_gaps, block_cols)
+    lib.cl_msa_columns_compute.restype = C.c_int
+    lib.cl_msa_columns_compute.argtypes = [C.c_void_p, C.POINTER(BaseGraphC), C.POINTER(MsaColumnsParams), C.POINTER(MsaColumnsC)]
+    ctx._check(lib.cl_msa_columns_compute(ctx.handle, C.byref(g), C.byref(p), C.byref(out)))
+    return _take_msa_columns(lib, out, len(graph.label))
+
+
 def alignment_distances(stats, n):
     """cl_alignment_distances (host only): the [n, n] float64 matrix d = 1 - 2 eq / (2 eq + 2 x + ins + del) of the n * (n - 1) / 2 rows of `stats`
     (induced_pairwise_stats of the pairs (a, b), a < b, a outer)"""
@@ -1338,7 +1447,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 18    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 19    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1556,6 +1665,7 @@ EXPORTED_SYMBOLS = [
     "cl_induced_pairwise_stat", "cl_induced_pairwise_stats", "cl_alignment_distances", "cl_refine_guide_tree",
     "cl_induced_pairwise_profile", "cl_induced_pairwise_profiles", "cl_induced_gap_events", "cl_induced_gap_events_batch",
     "cl_induced_pairwise_agreement", "cl_induced_pairwise_agreements",
+    "cl_msa_columns_params_default", "cl_msa_column_layout", "cl_msa_columns_host", "cl_msa_columns_compute", "cl_msa_columns_free", "cl_msa_columns_layout_seconds",
 ]
 
 

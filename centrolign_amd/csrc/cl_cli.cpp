@@ -13,6 +13,8 @@
 //     cl_induced_gap_events_batch on the printed graph); not with -c, whose final graph has cycles;
 //   - --compare-to GFA with --pair-agreement FILE writes, for every pair of sequences, how many aligned base pairs the printed graph shares with a
 //     baseline graph of the same sequences (cl_induced_pairwise_agreements); --graph GFA compares a graph that is already there instead of aligning;
+//   - --msa-out, --column-stats and --variable-sites write the alignment as columns: aligned FASTA, a record per column, and the aligned FASTA of
+//     the variable sites alone (cl_msa_columns_compute on the printed graph; --msa-layout, --site-min-minor, --site-max-gaps); not with -c;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -236,6 +238,80 @@ bool write_pair_positions(cl_context* ctx, const char* gfa, uint64_t gfa_len, co
     return true;
 }
 
+// a whole number >= 0 (--site-max-gaps)
+bool parse_count(const std::string& text, uint64_t& out) {
+    if (text.empty() || text.size() > 18) return false;
+    for (char c : text) if (c < '0' || c > '9') return false;
+    out = strtoull(text.c_str(), nullptr, 10);
+    return true;
+}
+
+// --msa-out / --column-stats / --variable-sites: the GFA text the run printed is read back (cl_read_gfa, as above) and goes through one
+// cl_msa_columns_compute call that makes what the files named need; entries in the printed graph's path order under the paths' names
+bool write_msa_columns(cl_context* ctx, const char* gfa, uint64_t gfa_len, const std::string& msa_file, const std::string& stats_file, const std::string& sites_file,
+                       int layout, uint32_t min_minor, uint32_t max_gaps, std::string& err) {
+    cl_owned_base_graph* owned = nullptr;
+    char** path_names = nullptr;
+    uint64_t n_paths = 0;
+    if (cl_read_gfa(gfa, gfa_len, 1, &owned, &path_names, &n_paths)) { err = "cannot read back the alignment graph"; return false; }
+    struct FreeGraph { cl_owned_base_graph* g; ~FreeGraph() { cl_owned_base_graph_free(g); } } free_graph{owned};
+    std::vector<std::string> names;
+    for (uint64_t p = 0; p < n_paths; ++p) { names.emplace_back(path_names[p]); free(path_names[p]); }
+    free(path_names);
+    cl_base_graph g;
+    cl_owned_base_graph_view(owned, &g);
+    cl_msa_columns_params params;
+    cl_msa_columns_params_default(&params);
+    params.layout = layout;
+    params.want = (msa_file.empty() ? 0u : 1u) | (stats_file.empty() ? 0u : 2u) | (sites_file.empty() ? 0u : 4u);
+    params.min_minor = min_minor;
+    params.max_gaps = max_gaps;
+    const auto t0 = std::chrono::steady_clock::now();
+    cl_msa_columns m;
+    if (cl_msa_columns_compute(ctx, &g, &params, &m)) {
+        const char* e = cl_last_error(ctx);
+        err = std::string("the alignment graph as columns: ") + (e && *e ? e : "failed");
+        return false;
+    }
+    struct FreeColumns { cl_msa_columns* m; ~FreeColumns() { cl_msa_columns_free(m); } } free_columns{&m};
+    {
+        char line[200];
+        snprintf(line, sizeof(line), "The alignment as columns (%s layout): %llu column(s)%s in %.3f s.", layout == 0 ? "level" : "node", (unsigned long long)m.n_cols,
+                 sites_file.empty() ? "" : (", " + std::to_string(m.n_sites) + " variable site(s)").c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        log_line(LOG_VERBOSE, line);
+    }
+    auto write_file = [&](const std::string& name, const std::string& text) {
+        std::ofstream out(name, std::ios::binary);
+        if (out) out.write(text.data(), (std::streamsize)text.size());
+        out.close();
+        if (!out) err = "could not write to " + name;
+        return (bool)out;
+    };
+    auto fasta = [&](const char* rows, uint64_t width) {
+        std::string text;
+        for (uint64_t p = 0; p < n_paths; ++p) {
+            text += '>'; text += names[p]; text += '\n';
+            text.append(rows + p * width, width);
+            text += '\n';
+        }
+        return text;
+    };
+    if (!msa_file.empty() && !write_file(msa_file, fasta(m.rows, m.n_cols))) return false;
+    if (!stats_file.empty()) {
+        std::string tsv = "column\tA\tC\tG\tT\tN\tgaps\tconsensus\tsite\n";
+        for (uint64_t c = 0; c < m.n_cols; ++c) {
+            const cl_msa_column& r = m.columns[c];
+            char num[160];
+            snprintf(num, sizeof(num), "%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%c\t%u\n", (unsigned long long)c, r.count[0], r.count[1], r.count[2], r.count[3], r.count[4], r.gaps,
+                     "ACGTN-"[r.consensus], r.flags & 1u);
+            tsv += num;
+        }
+        if (!write_file(stats_file, tsv)) return false;
+    }
+    if (!sites_file.empty() && !write_file(sites_file, fasta(m.site_rows, m.n_sites))) return false;
+    return true;
+}
+
 // a GFA text as the graph the comparisons read (cl_read_gfa, as above) with its path names
 struct NamedGraph {
     cl_owned_base_graph* owned = nullptr;
@@ -364,12 +440,18 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --compare-to GFA            With --pair-agreement, the baseline graph of the same sequences: an earlier run's, the reference's, a truth graph\n");
     fprintf(o, " --pair-agreement FILE       Write the aligned base pairs of every pair of sequences here, in the baseline and in both, to FILE (which must not exist yet; not with -c)\n");
     fprintf(o, " --graph GFA                 With --compare-to and --pair-agreement, compare GFA as the graph this run would have printed: nothing is aligned or printed\n");
+    fprintf(o, " --msa-out FILE              Write the alignment as aligned FASTA, one row per sequence, to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --column-stats FILE         Write the base and gap counts, the consensus and the site flag of every alignment column to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --variable-sites FILE       Write the aligned FASTA of the variable sites alone, the site = 1 columns of --column-stats, to FILE (which must not exist yet; not with -c)\n");
+    fprintf(o, " --msa-layout WORD           With the three above, the columns: level (compact, bubble branches side by side) or node (one graph node per column) [level]\n");
+    fprintf(o, " --site-min-minor INT        A column is a variable site if its second most frequent base occurs at least INT times [1]\n");
+    fprintf(o, " --site-max-gaps INT         ... and it has at most INT gaps [no limit]\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
     fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats, --dist-out, --pair-profile, --window,\n");
-    fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement and --graph are added; -v gates this tool's own\n");
-    fprintf(o, "progress lines. See README.md.\n");
+    fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement, --graph, --msa-out, --column-stats, --variable-sites, --msa-layout,\n");
+    fprintf(o, "--site-min-minor and --site-max-gaps are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -392,14 +474,16 @@ int run(int argc, char** argv) {
 
     std::string config_name;
     std::string tree_out, pair_stats, dist_out, refine_arg, pair_profile, pair_events, window_arg, min_event_arg, compare_to, pair_agreement, graph_name;
-    bool have_graph = false;
+    std::string msa_out, column_stats, variable_sites, msa_layout_arg, site_min_minor_arg, site_max_gaps_arg;
+    bool have_graph = false, have_msa_layout = false, have_site_min_minor = false, have_site_max_gaps = false;
     bool force_gfa_output = false, generate_config = false, infer_tree = false, have_window = false, have_min_event = false;
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
            OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009,
            OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013,
-           OPT_COMPARE_TO = 1014, OPT_PAIR_AGREEMENT = 1015, OPT_GRAPH = 1016 };
+           OPT_COMPARE_TO = 1014, OPT_PAIR_AGREEMENT = 1015, OPT_GRAPH = 1016,
+           OPT_MSA_OUT = 1017, OPT_COLUMN_STATS = 1018, OPT_VARIABLE_SITES = 1019, OPT_MSA_LAYOUT = 1020, OPT_SITE_MIN_MINOR = 1021, OPT_SITE_MAX_GAPS = 1022 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -434,6 +518,12 @@ int run(int argc, char** argv) {
         {"compare-to", required_argument, nullptr, OPT_COMPARE_TO},
         {"pair-agreement", required_argument, nullptr, OPT_PAIR_AGREEMENT},
         {"graph", required_argument, nullptr, OPT_GRAPH},
+        {"msa-out", required_argument, nullptr, OPT_MSA_OUT},
+        {"column-stats", required_argument, nullptr, OPT_COLUMN_STATS},
+        {"variable-sites", required_argument, nullptr, OPT_VARIABLE_SITES},
+        {"msa-layout", required_argument, nullptr, OPT_MSA_LAYOUT},
+        {"site-min-minor", required_argument, nullptr, OPT_SITE_MIN_MINOR},
+        {"site-max-gaps", required_argument, nullptr, OPT_SITE_MAX_GAPS},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -478,6 +568,12 @@ int run(int argc, char** argv) {
         case OPT_COMPARE_TO: compare_to = optarg; break;
         case OPT_PAIR_AGREEMENT: pair_agreement = optarg; break;
         case OPT_GRAPH: graph_name = optarg; have_graph = true; break;
+        case OPT_MSA_OUT: msa_out = optarg; break;
+        case OPT_COLUMN_STATS: column_stats = optarg; break;
+        case OPT_VARIABLE_SITES: variable_sites = optarg; break;
+        case OPT_MSA_LAYOUT: msa_layout_arg = optarg; have_msa_layout = true; break;
+        case OPT_SITE_MIN_MINOR: site_min_minor_arg = optarg; have_site_min_minor = true; break;
+        case OPT_SITE_MAX_GAPS: site_max_gaps_arg = optarg; have_site_max_gaps = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -515,6 +611,8 @@ int run(int argc, char** argv) {
             if (!config_value(cfg, name).empty()) return fail("--graph cannot be combined with another output option (-A, -S, -s, --bond-prefix)");
         if (!tree_out.empty() || !pair_stats.empty() || !dist_out.empty() || !pair_profile.empty() || !pair_events.empty() || have_window || have_min_event)
             return fail("--graph cannot be combined with another output option (--tree-out, --pair-stats, --dist-out, --pair-profile, --pair-events)");
+        if (!msa_out.empty() || !column_stats.empty() || !variable_sites.empty() || have_msa_layout || have_site_min_minor || have_site_max_gaps)
+            return fail("--graph cannot be combined with another output option (--msa-out, --column-stats, --variable-sites)");
     }
 
     if (!config_name.empty()) {
@@ -562,6 +660,40 @@ int run(int argc, char** argv) {
         return fail("--pair-agreement names the file of another output option");
     if (agreement && config_value(cfg, "cyclize_tandem_duplications") == "true")
         return fail("--compare-to and --pair-agreement cannot be combined with -c: the final graph then has cycles");
+    // --msa-out / --column-stats / --variable-sites, checked the same way
+    const bool msa_columns = !msa_out.empty() || !column_stats.empty() || !variable_sites.empty();
+    const bool msa_sites = !column_stats.empty() || !variable_sites.empty();
+    int msa_layout = 0;
+    uint64_t site_min_minor = 1, site_max_gaps = 0xFFFFFFFFull;
+    if (have_msa_layout && !msa_columns) return fail("--msa-layout needs --msa-out, --column-stats or --variable-sites");
+    if ((have_site_min_minor || have_site_max_gaps) && !msa_sites)
+        return fail(std::string(have_site_min_minor ? "--site-min-minor" : "--site-max-gaps") + " needs --column-stats or --variable-sites");
+    if (have_msa_layout) {
+        if (msa_layout_arg == "level") msa_layout = 0;
+        else if (msa_layout_arg == "node") msa_layout = 1;
+        else return fail("--msa-layout expects level or node, got '" + msa_layout_arg + "'");
+    }
+    if (have_site_min_minor && !parse_positive(site_min_minor_arg, site_min_minor))
+        return fail("--site-min-minor expects a whole number of sequences, at least 1, got '" + site_min_minor_arg + "'");
+    if (have_site_max_gaps && !parse_count(site_max_gaps_arg, site_max_gaps))
+        return fail("--site-max-gaps expects a whole number of sequences, at least 0, got '" + site_max_gaps_arg + "'");
+    site_min_minor = std::min<uint64_t>(site_min_minor, 0xFFFFFFFFull);   // (more than any number of sequences either way)
+    site_max_gaps = std::min<uint64_t>(site_max_gaps, 0xFFFFFFFFull);
+    if (!msa_out.empty() && std::ifstream(msa_out).good()) return fail("MSA file already exists: " + msa_out);
+    if (!column_stats.empty() && std::ifstream(column_stats).good()) return fail("Column statistics file already exists: " + column_stats);
+    if (!variable_sites.empty() && std::ifstream(variable_sites).good()) return fail("Variable sites file already exists: " + variable_sites);
+    if (msa_columns) {
+        const std::string* mine[3] = {&msa_out, &column_stats, &variable_sites};
+        const std::string others[7] = {pair_stats, dist_out, pair_profile, pair_events, pair_agreement, tree_out, config_value(cfg, "subalignments_filepath")};
+        for (int a = 0; a < 3; ++a) {
+            if (mine[a]->empty()) continue;
+            for (int b = a + 1; b < 3; ++b) if (*mine[a] == *mine[b]) return fail("--msa-out, --column-stats and --variable-sites must name different files");
+            for (const std::string& other : others)
+                if (*mine[a] == other) return fail("--msa-out, --column-stats and --variable-sites cannot name the file of another output option");
+        }
+        if (config_value(cfg, "cyclize_tandem_duplications") == "true")
+            return fail("--msa-out, --column-stats and --variable-sites cannot be combined with -c: the final graph then has cycles");
+    }
     NamedGraph baseline, given;
     auto load_graph = [&](const std::string& name, const char* what, NamedGraph& into, std::string& err) {
         std::string text;
@@ -623,6 +755,8 @@ int run(int argc, char** argv) {
         return fail("--pair-profile and --pair-events need --force-gfa-output for two sequences: they read the graph that is printed");
     if (agreement && n_sequences == 2 && !force_gfa_output)
         return fail("--compare-to and --pair-agreement need --force-gfa-output for two sequences: they read the graph that is printed");
+    if (msa_columns && n_sequences == 2 && !force_gfa_output)
+        return fail("--msa-out, --column-stats and --variable-sites need --force-gfa-output for two sequences: they read the graph that is printed");
     if (!dist_out.empty()) {   // the rows name sequences as -A names its files: two names that differ only in '/' and '_' could not be told apart
         std::vector<std::string> flat = sequence_names;
         for (std::string& nm : flat) for (char& c : nm) if (c == '/') c = '_';
@@ -718,9 +852,12 @@ int run(int argc, char** argv) {
         agreement_ok = printed.load(text, len) ? write_pair_agreement(own.ctx, printed, baseline, pair_agreement, positions_err)
                                                : (positions_err = "cannot read back the alignment graph", false);
     }
+    bool columns_ok = true;
+    if (written && positions_ok && agreement_ok && msa_columns)
+        columns_ok = write_msa_columns(own.ctx, text, len, msa_out, column_stats, variable_sites, msa_layout, (uint32_t)site_min_minor, (uint32_t)site_max_gaps, positions_err);
     free(text);
     if (!written) return fail("could not write the alignment to standard output");
-    if (!positions_ok || !agreement_ok) return fail(positions_err);
+    if (!positions_ok || !agreement_ok || !columns_ok) return fail(positions_err);
     if (!dist_out.empty()) {
         std::string err;
         const bool ok = write_distances(stats_file, sequence_names, dist_out, err);

@@ -389,15 +389,6 @@ struct InducedChunk {
     const uint32_t* d_tables;
 };
 
-// A device array that is released where it goes out of scope (DevBuf itself has no destructor)
-template <class T>
-struct ScopedBuf : DevBuf<T> {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf&) = delete;
-    ScopedBuf& operator=(const ScopedBuf&) = delete;
-    ~ScopedBuf() { this->release(); }
-};
-
 // A graph on the device for the passes over pairs of its paths: paths and labels, uploaded once and only when a pair needs them, and what is
 // known about each path — node ids out of range (found on the host, once per path) and nodes met twice (found on the device with the tables)
 struct InducedGraph {

@@ -280,6 +280,15 @@ struct DevBuf {
     }
 };
 
+// A device array that is released where it goes out of scope (DevBuf itself has no destructor)
+template <class T>
+struct ScopedBuf : DevBuf<T> {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf&) = delete;
+    ScopedBuf& operator=(const ScopedBuf&) = delete;
+    ~ScopedBuf() { this->release(); }
+};
+
 
 // Host arrays of tens to hundreds of megabytes that are filled completely right after they are made (the record and query tables of a
 // chaining DP: 1.2 GB at the root of a ten-sequence tree): std::vector would zero them first, single-threaded, and malloc hands such blocks
@@ -384,6 +393,19 @@ hipError_t cl_launch_induced_partner(const ClInducedJob* jobs, uint32_t n_jobs, 
                                      const uint32_t* tables, uint32_t* partner, uint64_t* counts, hipStream_t stream);
 hipError_t cl_launch_induced_agreement(const ClInducedJob* jobs, uint32_t n_jobs, const uint32_t* path_nodes, uint64_t n_steps, const uint8_t* label, uint64_t n_nodes,
                                        const uint32_t* tables, const uint32_t* partner, const uint64_t* counts, cl_pair_agreement* out, hipStream_t stream);
+
+// msa_columns_kernels.hip: one block of columns [c0, c0 + width) of the MSA matrix in a tile of n_paths rows of `stride` bytes (a multiple of 4, at least
+// width; preset to '-') (cl_columns_api.cpp).  range: per path the steps [lo, hi) whose columns fall into the block, max_steps the longest such range.
+// Sites: the counting pass writes counts[cl_msa_site_groups(width)]; the write pass takes their exclusive offsets and puts the block's k-th site at
+// site_col[k] and site_rows[p * n_block_sites + k]
+hipError_t cl_launch_msa_fill(const uint32_t* path_nodes, const uint64_t* range, uint64_t n_paths, uint64_t max_steps, const uint8_t* label,
+                              const uint32_t* node_col, uint32_t c0, uint32_t width, uint64_t stride, char* tile, hipStream_t stream);
+hipError_t cl_launch_msa_reduce(const char* tile, uint64_t n_paths, uint64_t stride, uint32_t width, uint32_t min_minor, uint32_t max_gaps,
+                                cl_msa_column* records, hipStream_t stream);
+uint32_t cl_msa_site_groups(uint32_t width);
+hipError_t cl_launch_msa_sites(bool write, const cl_msa_column* records, uint32_t width, uint32_t* counts, const uint32_t* offsets, uint64_t c0,
+                               const char* tile, uint64_t stride, uint64_t n_paths, uint64_t n_block_sites, uint64_t* site_col, char* site_rows,
+                               hipStream_t stream);
 
 // subaln_kernels.hip: the -s lines of one merge (cl_subaln_api.cpp).  One side of the merge on the device: the per-node step table
 // ((path << 32) | step of the node's first occurrence, UINT64_MAX: on no path), the labels, and the path names back to back

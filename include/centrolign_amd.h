@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 18   /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 19  /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -705,6 +705,54 @@ typedef struct cl_pair_agreement {
 int cl_induced_pairwise_agreement(const cl_base_graph* a, uint64_t a1, uint64_t a2, const cl_base_graph* b, uint64_t b1, uint64_t b2, cl_pair_agreement* out);
 int cl_induced_pairwise_agreements(cl_context* ctx, const cl_base_graph* a, const cl_base_graph* b, const uint64_t* quads /* [4 * n]: a1, a2, b1, b2 */, uint64_t n,
                                    cl_pair_agreement* out /* [n] */);
+/* The MSA as columns: which bases of all paths stand in one column, how conserved the column is, which columns are variable sites.  Read off
+ * labels and paths only, like the calls above (a graph without edges is a valid input).
+ *   Path edges: every two consecutive steps of every path.  A node is used if it lies on a path.  level(v) = 0 for a used node without an
+ *     in-edge among them, otherwise 1 + the largest level of a predecessor.  CL_ERR_CYCLIC_GRAPH if the path edges have a cycle (a path meets a
+ *     node twice, two paths meet two nodes in opposite order).  Along every path the level strictly increases.
+ *   Layout 0 (level): col(v) = level(v), n_cols = 1 + the largest level (0 without a used node).  The compact layout: the two nodes of a SNP
+ *     bubble share a column; branches of unequal length are left-justified against one another, so bases of different nodes in one column
+ *     are only placed together (the graph claims homology for the bases of one node only).
+ *   Layout 1 (node): col(v) = the number of used nodes u with (level(u), u) before (level(v), v), n_cols = the number of used nodes.  The
+ *     strict layout: one node per column, a topological order that depends on no traversal's tie rule.
+ *   An unused node has column 0xFFFFFFFF under both layouts.
+ *   rows: n_paths x n_cols bytes, row-major; rows[p][col(v)] = "ACGTN"[label(v)] for every step v of path p, '-' elsewhere.
+ *   columns[c]: the counts of A, C, G, T, N in column c, gaps = n_paths minus their sum, consensus = the first of A, C, G, T, N, gap (codes
+ *     0..5) with the largest count, flags bit 0: a site — the second largest of count[0..3] is at least min_minor and gaps is at most
+ *     max_gaps —, bit 1: gaps above 0, bit 2: count[4] above 0.
+ *   site_col: the columns with flags bit 0, ascending; site_rows: n_paths x n_sites bytes with site_rows[p][k] = rows[p][site_col[k]].
+ * want: bit 0 rows, bit 1 columns, bit 2 sites (site_col and site_rows; n_sites is 0 without it).  An array that is wanted is malloc'ed and
+ * never NULL on success, also when it is empty; one that is not wanted is NULL.  node_col always comes back.  n_paths == 0 succeeds with
+ * n_cols == 0.  CL_ERR_INVALID_ARGUMENT: a layout other than 0 or 1, unknown bits in want, min_minor == 0, a path node >= n_nodes, a label
+ * above 4 on a path, 2^32 paths or more, n_cols >= 2^32 - 1.
+ * cl_msa_column_layout: host only; the Kahn pass over the path edges both calls below begin with (a dependent chain as long as the graph).
+ * cl_msa_columns_host: host only, the definition.  cl_msa_columns_compute: the matrix is built on the device in blocks of block_cols columns
+ * (0: the largest multiple of 256 with n_paths x block_cols <= 256 MB, at least 256) and lives only in a device tile of that size
+ * (msa_columns_kernels.hip); rows come back block by block only when they are wanted.  The results are those of cl_msa_columns_host byte for
+ * byte, whatever block_cols is. */
+typedef struct cl_msa_column { uint32_t count[5], gaps, consensus, flags; } cl_msa_column;   /* 32 bytes */
+typedef struct cl_msa_columns_params {
+    int32_t  layout;      /* 0 level, 1 node */
+    uint32_t want;        /* bit 0 rows, bit 1 columns, bit 2 sites */
+    uint32_t min_minor;   /* >= 1 */
+    uint32_t max_gaps;
+    uint64_t block_cols;  /* 0: default */
+} cl_msa_columns_params;
+typedef struct cl_msa_columns {
+    uint64_t n_paths, n_cols, n_sites;
+    uint32_t* node_col;        /* [n_nodes] */
+    char* rows;                /* NULL unless wanted */
+    cl_msa_column* columns;    /* NULL unless wanted */
+    uint64_t* site_col;        /* NULL unless sites are wanted */
+    char* site_rows;
+} cl_msa_columns;
+void cl_msa_columns_params_default(cl_msa_columns_params* params);   /* level, all three, min_minor 1, max_gaps UINT32_MAX, block_cols 0 */
+int  cl_msa_column_layout(const cl_base_graph* graph, int layout, uint32_t* node_col /* [n_nodes] */, uint64_t* n_cols_out);
+int  cl_msa_columns_host(const cl_base_graph* graph, const cl_msa_columns_params* params, cl_msa_columns* out);
+int  cl_msa_columns_compute(cl_context* ctx, const cl_base_graph* graph, const cl_msa_columns_params* params, cl_msa_columns* out);
+void cl_msa_columns_free(cl_msa_columns* out);
+/* the wall time of the level pass inside this thread's last cl_msa_columns_host or cl_msa_columns_compute call: its share of the call */
+double cl_msa_columns_layout_seconds(void);
 /* The -A output of the CLI after cyclisation (src/core.cpp:537-545): output_maf(induced_cyclic_pairwise_alignment(graph, path1, path2), graph,
  * path1, path2) (src/alignment.cpp:569-904) — blocks of colinear alignment between the two paths of a graph that may have cycles; name1 / name2
  * stand for BaseGraph::path_name.  Host code, safe to call from several threads at once. */
