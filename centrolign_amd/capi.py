@@ -1447,7 +1447,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 19    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 20    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1587,6 +1587,14 @@ def load_library(path=None):
     lib.cl_match_joined_text.argtypes = [C.POINTER(BaseGraphC), C.POINTER(BaseGraphC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.cl_suffix_array_lcp.restype = C.c_int
     lib.cl_suffix_array_lcp.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.cl_device_sort_pairs.restype = C.c_int
+    lib.cl_device_sort_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.cl_device_inclusive_sum.restype = C.c_int
+    lib.cl_device_inclusive_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.cl_chain_value_index.restype = C.c_int
+    lib.cl_chain_value_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.cl_chain_value_index_host.restype = C.c_int
+    lib.cl_chain_value_index_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.cl_matches_from_suffix_array.restype = C.c_int
     lib.cl_matches_from_suffix_array.argtypes = [C.POINTER(BaseGraphC), C.POINTER(BaseGraphC), C.POINTER(MatchParams), C.c_void_p, C.c_void_p,
                                                  C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(MatchStats)]
@@ -1627,6 +1635,21 @@ def load_library(path=None):
     return lib
 
 
+def chain_value_index_host(values):
+    """cl_chain_value_index_host (host only): the chaining traceback's value index of float32 `values` as a small DP builds it — (keys int32, recs
+    uint32): recs = the record numbers in ascending order of value (-0.0 == +0.0, equal values in record order), keys[i] = the order-preserving
+    integer encoding of values[recs[i]]"""
+    lib = load_library()
+    values = np.ascontiguousarray(values, np.float32)
+    n = len(values)
+    keys, recs = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    rc = lib.cl_chain_value_index_host(values.ctypes.data, n, keys.ctypes.data, recs.ctypes.data)
+    if rc != 0:
+        msg = lib.cl_last_error(None)
+        raise ClError(rc, msg.decode() if msg else "")
+    return keys, recs
+
+
 def fallback_counters(reset=False):
     """cl_fallback_counters: dict(strip_fallbacks, walk_stalls, chain_dps, stitch_plans, strip_pairs, bond_trims_past_the_end) of this process"""
     lib = load_library()
@@ -1656,6 +1679,7 @@ EXPORTED_SYMBOLS = [
     "cl_estimate_score_scale", "cl_leaf_intrinsic_scale", "cl_leaf_graph", "cl_explicit_cigar", "cl_write_gfa",
     "cl_fuse", "cl_owned_base_graph_view", "cl_owned_base_graph_free", "cl_merge_params_default", "cl_merge", "cl_merge_result_free",
     "cl_match_params_default", "cl_find_matches", "cl_match_joined_text", "cl_suffix_array_lcp", "cl_matches_from_suffix_array",
+    "cl_device_sort_pairs", "cl_device_inclusive_sum", "cl_chain_value_index", "cl_chain_value_index_host",
     "cl_bond_params_default", "cl_identify_bonds", "cl_bonds_free", "cl_leaf_calibrate", "cl_leaf_calibration_free", "cl_alignment_list_free",
     "cl_leaf_bond_alignments", "cl_simplify_bubbles", "cl_apply_bonds", "cl_polish_params_default", "cl_identify_inconsistencies",
     "cl_polish_cyclized_graph",
@@ -2060,6 +2084,36 @@ class Context:
         rounds = C.c_uint32(0)
         self._check(self.lib.cl_suffix_array_lcp(self.handle, text.ctypes.data, n, sa.ctypes.data, lcp.ctypes.data, isa.ctypes.data, C.byref(rounds)))
         return sa, lcp, isa, int(rounds.value)
+
+    def sort_pairs(self, keys, vals, begin_bit=0, end_bit=None):
+        """cl_device_sort_pairs: the device's stable radix sort (csrc/cl_radix.h) of (keys: uint32 or uint64, vals: uint32) by key bits [begin_bit, end_bit)
+        (end_bit None: the key's width); returns (keys_out, vals_out) — whole keys, pairs of equal bits in input order"""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
+            raise TypeError("keys must be uint32 or uint64, not %s" % keys.dtype)
+        vals = np.ascontiguousarray(vals, np.uint32)
+        if len(vals) != len(keys):
+            raise ValueError("%d keys, %d values" % (len(keys), len(vals)))
+        end_bit = 8 * keys.dtype.itemsize if end_bit is None else end_bit
+        keys_out, vals_out = np.zeros_like(keys), np.zeros_like(vals)
+        self._check(self.lib.cl_device_sort_pairs(self.handle, keys.dtype.itemsize, keys.ctypes.data, vals.ctypes.data, len(keys), int(begin_bit), int(end_bit),
+                                                  keys_out.ctypes.data, vals_out.ctypes.data))
+        return keys_out, vals_out
+
+    def inclusive_sum(self, values):
+        """cl_device_inclusive_sum: the device's inclusive prefix sum (csrc/cl_radix.h) of uint32 `values`, modulo 2^32"""
+        values = np.ascontiguousarray(values, np.uint32)
+        out = np.zeros_like(values)
+        self._check(self.lib.cl_device_inclusive_sum(self.handle, values.ctypes.data, len(values), out.ctypes.data))
+        return out
+
+    def chain_value_index(self, values):
+        """cl_chain_value_index: chain_value_index_host's (keys, recs) as the device builds them for a large DP (csrc/chain_sort.hip)"""
+        values = np.ascontiguousarray(values, np.float32)
+        n = len(values)
+        keys, recs = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        self._check(self.lib.cl_chain_value_index(self.handle, values.ctypes.data, n, keys.ctypes.data, recs.ctypes.data))
+        return keys, recs
 
     def anchor_chain(self, graph1, graph2, matches, max_num_match_pairs=1250000, score_scale=1.0, autocalibrate=True,
                      params=None, fill_in=True, chaining_algorithm=None):

@@ -79,6 +79,16 @@ using clhost::min_source_sink;
 inline int enc(float f) { int b; memcpy(&b, &f, 4); if (b == (int)0x80000000) b = 0; return b >= 0 ? b : b ^ 0x7FFFFFFF; }   // -0.0f == +0.0f, as on the device
 inline float dec(int k) { int b = k >= 0 ? k : k ^ 0x7FFFFFFF; float f; memcpy(&f, &b, 4); return f; }
 
+// the value index of n stored values, built on the host: recs = the record numbers in ascending order of enc(value), equal keys in record order, and
+// keys[i] = enc(val[recs[i]]) — the same order as the device's stable radix sort (chain_sort.hip).  ChainTrace::value_index for a small DP, and
+// cl_chain_value_index_host, through which the tests hold the two against each other
+inline void value_index_host(const float* val, uint32_t n, int* keys, uint32_t* recs) {
+    std::vector<int> key(n);
+    for (uint32_t r = 0; r < n; ++r) { key[r] = enc(val[r]); recs[r] = r; }
+    std::stable_sort(recs, recs + n, [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    for (uint32_t i = 0; i < n; ++i) keys[i] = key[recs[i]];
+}
+
 // heap node of the r-th smallest key in a MaxSearchTree / outer OrthogonalMaxSearchTree of n keys
 // (implicit complete binary tree filled by an in-order walk, max_search_tree.hpp:113-150)
 inline std::vector<uint32_t> heap_of_rank(size_t n) {

@@ -102,14 +102,9 @@ bool ChainTrace::value_index(const ChainProblem& P, ChainDev& dev, size_t ci, in
     if (dev.d_pack.p) {
         // a small DP: the stored values came back with the DP values; the same order as the device's stable radix sort
         const float* val = reinterpret_cast<const float*>(dev.pack_host.data() + ((char*)dev.cd[ci].d_val.p - dev.d_pack.p - dev.pack_dp_off)) + (size_t)kind * n;
-        auto& recs = vrecs[ci][kind];
-        recs.resize(n);
-        std::iota(recs.begin(), recs.end(), 0u);
-        std::vector<int> key(n);
-        for (uint32_t r = 0; r < n; ++r) key[r] = enc(val[r]);
-        std::stable_sort(recs.begin(), recs.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+        vrecs[ci][kind].resize(n);
         vkeys[ci][kind].resize(n);
-        for (uint32_t i = 0; i < n; ++i) vkeys[ci][kind][i] = key[recs[i]];
+        value_index_host(val, n, vkeys[ci][kind].data(), vrecs[ci][kind].data());
         index_ms += ms_since(t);
         vbuilt[ci][kind] = 1;
         return true;

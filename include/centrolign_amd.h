@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 19  /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 20 /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -505,6 +505,24 @@ int cl_match_joined_text(const cl_base_graph* graph1, const cl_base_graph* graph
 int cl_suffix_array_lcp(cl_context* ctx, const uint8_t* text, uint64_t n, uint32_t* sa, uint32_t* lcp, uint32_t* isa, uint32_t* rounds_out);
 int cl_matches_from_suffix_array(const cl_base_graph* graph1, const cl_base_graph* graph2, const cl_match_params* params, const uint32_t* sa,
                                  const uint32_t* lcp, uint64_t n, cl_owned_match_sets** out, cl_match_stats* stats /* may be NULL */);
+
+/* --- The device primitives under the suffix array, the guide tree's spectra, the far pass's static orders and the traceback's value index
+ * (csrc/cl_radix.h, csrc/chain_sort.hip), on host arrays: upload, one run on the context's stream, download; every device array is released on
+ * every return path.  They exist so that a test can hold each primitive against an exact reference.  CL_ERR_INVALID_ARGUMENT, with a message
+ * and without a launch: a NULL context, a NULL array with n > 0, n >= 2^32, and for the sort a key_bytes other than 4 or 8, end_bit <= begin_bit
+ * or end_bit > 8 * key_bytes.  n == 0 is CL_OK and touches nothing. */
+/* cl_device_sort_pairs: (keys_out, vals_out) = the n pairs (keys_in, vals_in) — keys of key_bytes = 4 (uint32_t) or 8 (uint64_t) bytes — in
+ * ascending order of key bits [begin_bit, end_bit); pairs whose bits agree keep their input order, and whole keys travel, the other bits untouched. */
+int cl_device_sort_pairs(cl_context* ctx, int key_bytes, const void* keys_in, const uint32_t* vals_in, uint64_t n, uint32_t begin_bit,
+                         uint32_t end_bit, void* keys_out, uint32_t* vals_out);
+/* cl_device_inclusive_sum: out[i] = in[0] + ... + in[i] modulo 2^32. */
+int cl_device_inclusive_sum(cl_context* ctx, const uint32_t* in, uint64_t n, uint32_t* out);
+/* cl_chain_value_index: the chaining traceback's value index of n stored DP values as the device builds it for a large DP: recs_out = the record
+ * numbers 0 .. n-1 in ascending order of value (-0.0 == +0.0; equal values in record order), keys_out[i] = the order-preserving integer
+ * encoding of values[recs_out[i]] (the float's bits, -0.0 folded onto +0.0, the low 31 bits flipped where negative).  The DP stores no NaN. */
+int cl_chain_value_index(cl_context* ctx, const float* values, uint32_t n, int32_t* keys_out, uint32_t* recs_out);
+/* cl_chain_value_index_host: the same index as the traceback builds it on the host for a small DP (std::stable_sort); no context, no device. */
+int cl_chain_value_index_host(const float* values, uint32_t n, int32_t* keys_out, uint32_t* recs_out);
 
 /* --- Anchorer::anchor_chain (include/centrolign/anchorer.hpp:135-145, 958-1329), no masks, after
  * cl_split_branching_matches (the caller runs it first, as anchor_chain does at :971-973): budgeted match selection (which REORDERS the caller's match sets, :1108-1173),
