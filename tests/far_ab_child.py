@@ -32,8 +32,9 @@ def params_from_row(row):
     return p
 
 
-def save_input(path, g1, g2, ms, scale, params=None):
+def save_input(path, g1, g2, ms, scale, params=None, extra=None):
     d = {"scale": np.array([scale])}
+    d.update(extra or {})      # (further arrays a child of its own reads: tests/pair_sweep_child.py)
     if params is not None:
         d["params"] = np.array([params_row(p) for p in params], np.float64).reshape(-1, 11)
     for tag, g in (("g1.", g1), ("g2.", g2)):

@@ -457,6 +457,7 @@ def sweep_result_diff(res, z, prefix, check_score, check_choice):
 # paths of graph 1 x paths of graph 2 on both sides of every count at which cl_chain_device.cpp (choose_path) changes its device path: 1 | 2 (the one-combination
 # specialisations), 8 | 9 (chain_walk2), 16 | 17 (granules | atomic maximum + arrival count), 256 | 257, 512 | 513, 768 | 770 (one, two, three combinations
 # per walk workgroup, then the group-by-group path), 4 096 | 4 160 tags (parallel | serial numbering), 65 535 | 65 536 (a launch dimension's limit)
+# (the other axis along which the driver changes its path, the number of match pairs, is pair_cases() at the end of this file)
 COMBO_PATHS = ((1, 1), (1, 2), (2, 2), (2, 4), (3, 3), (4, 4), (1, 17), (2, 9), (16, 16), (1, 257), (16, 32), (19, 27), (24, 32), (22, 35), (32, 33),
                (64, 64), (64, 65), (255, 257), (256, 256), (256, 257))
 COMBO_MULTI_MAX = 1056        # the multi-block size up to here
@@ -604,3 +605,172 @@ def combo_ref_can_run(case):
     """the compiled reference's sparse_affine_chain_dp did not finish within two minutes at 1 x 257 paths and 300 pairs (the oracle: 0.9 s): it is run on the
     cases with fewer than 256 paths on either side"""
     return max(case.p1, case.p2) < 256
+
+
+# the chaining DP across the number of match pairs ------------------------------------------------------------------------
+# (tests/test_pair_sweep.py, tests/test_gpu_pair_sweep.py, tests/pair_sweep_child.py)
+# pairs on both sides of every count at which cl_chain_device.cpp, chain_device.h or cl_chain_prep.cpp change what they do: a block of kChainBlock = 256 pairs; a
+# macro-block of kChainMacro = 1 024 (a walk launch whose count is partial, or 1); the far pass on from lag + 3 macro-blocks (4 096 | 4 097 at the default lag of 2,
+# (lag + 2) x 1 024 | + 1 under CL_CHAIN_FAR_LAG); the levels of the far pass's node tree (a largest combination of 512, 4 096, 32 768 records); one packed device
+# block | separate arrays (PackLayout::lay_out <= 2 MB); dense | factored query tables (combinations x pairs > 100 000); no pair at all
+PAIR_MACRO, PAIR_BLOCK, PAIR_PACK_BYTES, PAIR_FACTORED_ABOVE = 1024, 256, 2 << 20, 100000
+PAIR_COUNTS_ALL = (0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 3072, 3073, 4095, 4096, 4097, 5119, 5120, 5121)
+# the largest number of pairs at which a family's subset is still packed into one device block (pack_total below; tests/test_pair_sweep.py asserts both sides)
+PAIR_PACK_EDGE = {"A": 18624, "B": 5257, "C": 2496}
+# family -> (paths of graph 1, paths of graph 2, disjoint paths?, ancestor length, max_count of the match finder, seed of the full input, further pair counts)
+# A: one combination, records = pairs: the record-count edges are exact pair counts; the `simple` one-combination specialisations; packed up to its pack edge and
+#    on chain_walk2 beyond.  B: four combinations whose paths share nodes (the granule exchange); a pair leaves a record in about every combination.
+# C: sixteen combinations over paths that share no node: a pair lies in exactly one, so every combination decides values of its own; few records per combination
+#    (one-level and two-level trees, leaves of fewer than 64 records)
+PAIR_FAMILIES = {
+    "A": (1, 1, False, 300000, 6, 6100, (10240, 10241, PAIR_PACK_EDGE["A"], PAIR_PACK_EDGE["A"] + 1, 32767, 32768, 32769)),
+    "B": (2, 2, False, 300000, 6, 6200, (PAIR_PACK_EDGE["B"], PAIR_PACK_EDGE["B"] + 1)),
+    "C": (4, 4, True, 3000, 40, 6300, (PAIR_PACK_EDGE["C"], PAIR_PACK_EDGE["C"] + 1, 6250, 6251, 10240, 10241, 32768)),
+}
+PAIR_LOCAL_MAX = 5121        # local anchoring too up to here
+PAIR_EDGE_LIST = (255, 256, 257, 1023, 1024, 1025, 2049, 3073, 4096, 4097, 5121)      # the cases of the scheduling variants, in every family
+PAIR_FAR_LAGS = (1, 3, 8)    # CL_CHAIN_FAR_LAG: far pass off at (lag + 2) x 1 024 pairs, on at one more (families A and C)
+# the far-on cases whose DP values must depend on the far launches (B ends at its pack edge, C's largest case is 32 768).  Measured on an MI355X with the seeds above
+# under CL_CHAIN_DEBUG_SKIP_FAR=1, DP values that differ from the oracle's, affine / gap-free: A 106 / 62 of 4 097, 296 / 186 of 5 121, 7 338 / 7 310 of 32 769;
+# B 110 / 75 of 4 097, 298 / 238 of 5 121; C 41 / 27 of 4 097, 167 / 77 of 5 121, 11 749 / 12 253 of 32 768.  The first seed tried did for every family (the
+# next three of each gave, in the affine DP at 4 097 pairs and the three chain scales, 98 - 136 in A and B and 10 - 115 in C): even the 4 097-pair cases, whose
+# last macro-block is one pair, have dozens of pairs whose value depends on a predecessor that only a far launch sees.  (The gap-free DP's values
+# did not change at 4 097 pairs under one of those other seeds of C: a new seed needs the measurement again)
+PAIR_SKIP_FAR = {"A": (4097, 5121, 32769), "B": (4097, 5121), "C": (4097, 5121, 32768)}
+
+
+class PairCase:
+    """one input of the sweep: family, number of match pairs, chain scale"""
+
+    def __init__(self, family, n, scale):
+        self.family, self.n, self.scale = family, n, scale
+        self.name = "%s_%d" % (family, n)
+
+    def __repr__(self):
+        return self.name
+
+
+def pair_cases(family=None):
+    out = []
+    for fam in sorted(PAIR_FAMILIES):
+        counts = PAIR_COUNTS_ALL + PAIR_FAMILIES[fam][6]
+        assert len(set(counts)) == len(counts), fam
+        out += [PairCase(fam, n, CHAIN_SCALES[k % 3]) for k, n in enumerate(counts) if family in (None, fam)]
+    return out
+
+
+def pair_case(name):
+    return next(c for c in pair_cases() if c.name == name)
+
+
+_pair_full, _pair_inputs = {}, {}
+
+
+def pair_full_input(family, seed=None):
+    """(graph 1, graph 2, every match set) of a family, built once: combo_input's generator at the family's size (another seed: for choosing the family's)"""
+    if seed is not None:
+        return _pair_generate(family, seed)
+    if family not in _pair_full:
+        _pair_full[family] = _pair_generate(family, PAIR_FAMILIES[family][5])
+    return _pair_full[family]
+
+
+def _pair_generate(family, seed):
+    from oracle import pyoracle as po
+    p1, p2, disjoint, length, max_count, _, _ = PAIR_FAMILIES[family]
+    rng = np.random.default_rng(seed)
+    unit = rng.integers(0, 4, int(rng.integers(23, 48))).astype(np.uint8)
+    anc = np.tile(unit, length // len(unit) + 1)[:length].copy()
+    mut = rng.random(length) < 0.04
+    anc[mut] = rng.integers(0, 4, int(mut.sum()))
+    if disjoint:
+        g1, g2 = disjoint_paths_graph(anc, p1, seed, (5, 6)), disjoint_paths_graph(anc, p2, seed + 50000, (7, 8))
+    else:
+        g1 = synth.bubble_graph(anc, p1, seed=seed, alt_p=0.004, skip_p=0.0, sentinels=(5, 6))
+        g2 = synth.bubble_graph(anc, p2, seed=seed + 50000, alt_p=0.004, skip_p=0.0, sentinels=(7, 8))
+    return g1, g2, po.oracle_find_matches(g1, g2, max_count=max_count)
+
+
+def pair_input(case):
+    """(graph 1, graph 2, match sets, scale) of a PairCase: the family's full match sets thinned to EXACTLY the case's number of pairs"""
+    if case.name not in _pair_inputs:
+        from oracle import pyoracle as po
+        g1, g2, full = pair_full_input(case.family)
+        ms = po.budget_subset(full, case.n, seed=PAIR_FAMILIES[case.family][5])
+        assert ms.n_pairs() == case.n, "%s: the subset holds %d pairs" % (case.name, ms.n_pairs())
+        _pair_inputs[case.name] = (g1, g2, ms, case.scale)
+    return _pair_inputs[case.name]
+
+
+def combination_records(g1, g2, ms):
+    """[path of graph 1][path of graph 2] -> records of that combination in the affine DP (count_records, combination by combination)"""
+    per_set = []
+    for side, g in (("1", g1), ("2", g2)):
+        so, wo, nodes = (np.asarray(getattr(ms, k + side)).astype(np.int64) for k in ("set_off", "walk_off", "nodes"))
+        n_paths = len(g.path_off) - 1
+        on_end = _paths_on(g)[nodes[wo[1:] - 1]].astype(np.int64) if len(wo) > 1 else np.zeros((0, n_paths), np.int64)
+        below = np.concatenate([np.zeros((1, n_paths), np.int64), np.cumsum(on_end, axis=0)])
+        per_set.append(below[so[1:]] - below[so[:-1]])       # [set][path]: walks of the set that end on the path
+    return per_set[0].T @ per_set[1]
+
+
+def pack_total(n_pairs, combo_records, use_walk=True):
+    """bytes of the one device block of a small DP: PackLayout::lay_out (cl_chain_device.cpp) restated.  Every array is rounded up to 256 bytes; a combination is a
+    ClChainCombo of 96 bytes (a count and eleven pointers), its `prefix` holds n_blocks + 1 words"""
+    state = [0]
+
+    def reserve(nbytes):
+        state[0] += (nbytes + 255) & ~255
+    m, recs = n_pairs, [int(n) for n in combo_records]
+    n_blocks = (m + PAIR_BLOCK - 1) // PAIR_BLOCK
+    for n in recs:
+        for _ in range(4):
+            reserve(4 * n)                  # rec_s, ins_t, off, sigma
+        reserve(4 * (n_blocks + 1))         # prefix
+        for _ in range(3):
+            reserve(4 * m)                  # qt, qoff, q
+        if use_walk:
+            reserve(4 * m)                  # own
+    reserve(96 * len(recs))
+    for nbytes in (4 * m, 4 * m, 4 * (m + 1), 4 * sum(recs), 4 * sum(recs)):      # weight, init, rec_off, rec_combo, rec_pos
+        reserve(nbytes)
+    if use_walk:
+        reserve(len(recs) * PAIR_MACRO * 8)     # the granules of the exchange
+        reserve(32 * 4)                         # status
+    reserve(4 * m)                              # dp
+    for n in recs:
+        reserve(7 * n * 4)                      # val
+    for n in recs:
+        reserve(m * 7 * 4)                      # acc
+    return state[0]
+
+
+class PairPrediction:
+    """what the driver must do with a case, from its input alone (the affine DP, default switches, far lag 2 unless given)"""
+
+    def __init__(self, case, lag=2):
+        g1, g2, ms, _ = pair_input(case)
+        rec = combination_records(g1, g2, ms)
+        per_combo = sorted((int(n) for n in rec.ravel() if n), reverse=True)
+        self.pairs, self.combos, self.records, self.largest = case.n, len(per_combo), int(rec.sum()), per_combo[0] if per_combo else 0
+        self.n_macro = (case.n + PAIR_MACRO - 1) // PAIR_MACRO
+        self.far = self.n_macro >= lag + 3
+        # far_setup: leaves of 64 records, a fan-out of 8, four levels at the most; every combination padded to whole top-level nodes
+        self.levels = 1
+        while self.levels < 4 and (64 << (3 * self.levels)) <= self.largest:
+            self.levels += 1
+        n_top = 64 << (3 * (self.levels - 1))
+        self.padded = sum((n + n_top - 1) // n_top * n_top for n in per_combo)
+        self.pack_bytes = pack_total(case.n, per_combo) if per_combo else 0
+        self.packed = bool(per_combo) and self.pack_bytes <= PAIR_PACK_BYTES
+        self.walk = "2" if not self.packed and self.combos <= 8 else "1"
+        self.factored = self.combos * case.n > PAIR_FACTORED_ABOVE
+
+
+_pair_predictions = {}
+
+
+def pair_prediction(case):
+    if case.name not in _pair_predictions:
+        _pair_predictions[case.name] = PairPrediction(case)
+    return _pair_predictions[case.name]
