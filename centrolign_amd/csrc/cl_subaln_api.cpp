@@ -47,13 +47,13 @@ struct Text {
     }
 };
 
-// one graph of the merge on the device: paths, labels, names and the step table
+// one graph of the merge on the device: paths, labels, names and the step table; released where it goes out of scope
 struct DevSide {
-    DevBuf<uint64_t> path_off, name_off;
-    DevBuf<uint32_t> path_nodes;
-    DevBuf<uint8_t> label;
-    DevBuf<char> names;
-    DevBuf<unsigned long long> table;
+    ScopedBuf<uint64_t> path_off, name_off;
+    ScopedBuf<uint32_t> path_nodes;
+    ScopedBuf<uint8_t> label;
+    ScopedBuf<char> names;
+    ScopedBuf<unsigned long long> table;
     int load(cl_context* ctx, const cl_base_graph* g, const char* const* path_names, ClSubalnSide* view) {
         const uint64_t n_steps = g->path_off[g->n_paths];
         std::vector<uint64_t> noff(1, 0);
@@ -115,9 +115,9 @@ int cl_subalignment_text(cl_context* ctx, const cl_base_graph* g1, const char* c
         const uint64_t max_line = 2 * std::max<uint64_t>(5, longest + 13) + 2;
         const uint64_t per_chunk = std::min<uint64_t>(n_pairs, std::max<uint64_t>(1, (chunk_bytes ? chunk_bytes : kDefaultChunkBytes) / max_line));
         const uint64_t per_block = cl_subaln_pairs_per_block();
-        DevBuf<uint64_t> d_pairs, d_off;
-        DevBuf<unsigned long long> d_bad;
-        DevBuf<char> d_text;
+        ScopedBuf<uint64_t> d_pairs, d_off;   // (every return below gives the sixteen blocks back: cl_dev_free waits for the stream first)
+        ScopedBuf<unsigned long long> d_bad;
+        ScopedBuf<char> d_text;
         if ((rc = d_pairs.alloc(ctx, 2 * per_chunk)) || (rc = d_off.alloc(ctx, (per_chunk + per_block - 1) / per_block + 1)) || (rc = d_bad.alloc(ctx, 1)) ||
             (rc = d_text.alloc(ctx, per_chunk * max_line)))
             return rc;

@@ -1,6 +1,7 @@
 """The MSA as columns on the device: cl_msa_columns_compute (msa_columns_kernels.hip) against the host definition cl_msa_columns_host on the
 committed MSA graphs and on crafted paths — block seams, row counts around a wave, column counts around the reduce kernel's four columns a
-thread and 256 threads a workgroup, sites carried across workgroups and blocks —, its error codes, and the command line's --msa-out,
+thread and 256 threads a workgroup, sites carried across workgroups and blocks, 65 541 paths against the 65 535 grid rows over which
+msa_fill_kernel strides (and counts beyond 16 bits) —, its error codes, and the command line's --msa-out,
 --column-stats and --variable-sites.  Every comparison is exact."""
 import numpy as np
 import pytest
@@ -109,6 +110,43 @@ def test_gpu_row_counts_around_a_wave(gpu_ctx, n_paths):
         assert host["n_cols"] >= 280 and host["n_paths"] == n_paths   # (about 300: the backbone, less a deletion or two, plus insertions)
         for block_cols in (None, 100):
             same_as_host(capi.msa_columns(g, gpu_ctx, layout=layout, block_cols=block_cols), host, 7, (layout, block_cols))
+
+
+def many_paths_graph(P, W):
+    """P paths over a backbone of W columns with a SNP alternate in every column but the first and deletions of one to three columns from the
+    sixth on; numpy all the way (msa_like's loops take a second per thousand paths)"""
+    rng = np.random.default_rng(P)
+    labels = rng.integers(0, 4, W)
+    labels = np.concatenate([labels, (labels + rng.integers(1, 4, W)) % 4])   # node W + i: the other base of column i
+    alt = rng.random((P, W)) < 0.3
+    alt[:, 0] = False
+    start, length = rng.random((P, W)) < 0.02, rng.integers(1, 4, (P, W))
+    start[:, :5] = False
+    deleted = np.zeros((P, W), bool)
+    for s in range(3):
+        deleted[:, s:] |= (start & (length > s))[:, :W - s]
+    nodes = np.where(alt, W + np.arange(W), np.arange(W))
+    off = np.concatenate([[0], np.cumsum((~deleted).sum(1))]).astype(np.uint64)
+    z = np.zeros(2 * W + 1, np.uint64)
+    assert np.any(deleted)
+    return capi.BaseGraph(labels.astype(np.uint8), z, np.zeros(0, np.uint32), z, np.zeros(0, np.uint32), off, nodes[~deleted].astype(np.uint32), 0, 0)
+
+
+@pytest.mark.gpu
+def test_gpu_more_paths_than_grid_rows(gpu_ctx):
+    """65 541 paths over 40 columns: msa_fill_kernel's grid has 65 535 rows, so rows 0 .. 5 walk a second path each; and a column holds more
+    than 65 535 bases"""
+    P, W = 65541, 40
+    g = many_paths_graph(P, W)
+    assert len(g.path_off) - 1 == P > 65535 and int(g.path_off[-1]) > 2500000
+    for layout in tmc.LAYOUTS:
+        host = capi.msa_columns_host(g, layout=layout)
+        assert host["n_paths"] == P and host["n_cols"] == (W if layout == "level" else 2 * W - 1)   # (column 0 has no alternate)
+        assert int(host["columns"][:, :5].sum(1).max()) > 65535 and int(host["columns"][:, :4].max()) > 65535   # (no 16-bit count holds these)
+        if layout == "level":
+            assert host["n_sites"] > 30 and np.any(host["columns"][:, 5] > 0)
+        for block_cols in (None, 16):
+            same_as_host(capi.msa_columns(g, gpu_ctx, layout=layout, want=7, block_cols=block_cols), host, 7, (layout, block_cols))
 
 
 @pytest.mark.gpu

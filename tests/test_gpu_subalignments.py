@@ -1,6 +1,9 @@
 """-s on the device: cl_subalignment_text (subaln_kernels.hip) against a Python restatement of Core::emit_subalignment (src/core.cpp:424-472)
 on merge graphs and crafted path graphs; cl_msa's -s file, --bond-prefix files and --force-gfa-output against the compiled reference's
-(tests/golden/make_subalignments.py), at one and four workers."""
+(tests/golden/make_subalignments.py), at one and four workers.  test_gpu_block_at_the_sizes_of_a_real_merge reaches the branches that only
+a 1 Mbp merge does: 2 300 000 path steps, more than the 8 192 x 256 = 2 097 152 threads of subaln_step_table_kernel, whose grid-stride loop
+runs a second time; 263 000 pairs in one chunk, more than 1 024 x 256 = 262 144, hence 1 028 workgroup sums and a second tile (with a carry)
+in subaln_offsets_kernel, and a failing pair reported by a workgroup beyond the first tile; step numbers of one to seven digits."""
 import hashlib
 import json
 import os
@@ -144,6 +147,77 @@ def test_gpu_block_error_codes(gpu_ctx):
             capi.subalignment_text(gpu_ctx, g1, ["a", "b"], [], g2, ["c", "d"], [], p, chunk_bytes=4096)
         assert e.value.code == -1   # CL_ERR_INVALID_ARGUMENT
         assert "pair 1234 " in str(e.value) and what in str(e.value)
+
+
+def np_subalignment(g1, pn1, set1, g2, pn2, set2, pairs):
+    """py_subalignment for millions of steps: a node's first (path, step) is where the node first occurs in the flat step array, since that
+    array holds path 0's steps, then path 1's, each in step order.  Returns (bytes, the step of side 1 per pair, -1 for a gap)"""
+    def first_steps(g):
+        nodes, at = np.unique(g.path_nodes, return_index=True)
+        off = g.path_off.astype(np.int64)
+        path = np.searchsorted(off, at, side="right") - 1
+        p_of, s_of = np.full(len(g.label), -1, np.int64), np.full(len(g.label), -1, np.int64)
+        p_of[nodes], s_of[nodes] = path, at - off[path]
+        return p_of, s_of
+    pairs = np.asarray(pairs, np.uint64).reshape(-1, 2)
+    cols, steps1 = [], None
+    for g, names, col in ((g1, pn1, pairs[:, 0]), (g2, pn2, pairs[:, 1])):
+        p_of, s_of = first_steps(g)
+        gap = col == np.uint64(GAP)
+        v = np.where(gap, 0, col).astype(np.int64)
+        assert np.all(gap | (p_of[v] >= 0)), "a node on no path"
+        dec = list(DEC) + ["\0"]
+        cols.append(["-\t-\t-" if is_gap else "%s\t%d\t%s" % (names[p], s, dec[lab])
+                     for is_gap, p, s, lab in zip(gap.tolist(), p_of[v].tolist(), s_of[v].tolist(), np.minimum(g.label[v], 5).tolist())])
+        if steps1 is None:
+            steps1 = np.where(gap, -1, s_of[v])
+    head = ["# sequence set 1\n"] + [s + "\n" for s in set1] + ["# sequence set 2\n"] + [s + "\n" for s in set2] + ["# alignment\n"]
+    return "".join(head + [a + "\t" + b + "\n" for a, b in zip(*cols)]).encode(), steps1
+
+
+@pytest.mark.gpu
+def test_gpu_block_at_the_sizes_of_a_real_merge(gpu_ctx):
+    """graph 1: two paths over 2 200 000 nodes, 0 .. 1 099 999 and 1 000 000 .. 2 199 999 — 2 300 000 steps; the 100 000 shared nodes belong
+    to path 0 by the first-step rule.  263 000 pairs in one chunk, gaps on both sides, node picks drawn by the number of digits of their step
+    so that one to seven digits occur below and from pair 262 144 on (the second tile of the offset scan).  Then a node on no path at pairs
+    262 200 and 262 900: the smaller index, found by a workgroup beyond the first tile."""
+    rng = random.Random(31)
+    small1, on_small1 = crafted_graph(rng, 300, 3)
+    g2, on2 = crafted_graph(rng, 300, 3)
+    pn2 = ["q%d" % p for p in range(3)]
+    few = random_pairs(rng, on_small1, on2, 500, lead_gap=True, tail_gap=True)   # the restatement against py_subalignment, cyclic paths included
+    assert np_subalignment(small1, ["x0", "x1", "x2"], ["a"], g2, pn2, ["b"], few)[0] == py_subalignment(small1, ["x0", "x1", "x2"], ["a"], g2, pn2, ["b"], few)
+
+    nprng = np.random.default_rng(31)
+    n_nodes, n_pairs, tile = 2200000, 263000, 1024 * 256
+    g1 = path_graph(nprng.integers(0, 6, n_nodes), [np.arange(0, 1100000), np.arange(1000000, 2200000)])
+    assert int(g1.path_off[-1]) == 2300000 > 8192 * 256
+    # a step of d digits, on path 0 (node = step; for seven digits a shared node) or, from six digits on, on path 1 (node = step + 1 000 000)
+    d = nprng.integers(1, 8, n_pairs)
+    lo, hi = np.where(d == 1, 0, 10 ** (d - 1)), 10 ** d
+    on_path1 = (d >= 6) & (nprng.random(n_pairs) < 0.5)
+    hi = np.where(d == 7, np.where(on_path1, 1200000, 1100000), hi)
+    step = (lo + nprng.random(n_pairs) * (hi - lo)).astype(np.int64)
+    pairs = np.stack([np.where(on_path1, step + 1000000, step), nprng.choice(np.asarray(on2), n_pairs)], 1).astype(np.uint64)
+    r = nprng.random(n_pairs)
+    pairs[r < 0.15, 0] = GAP
+    pairs[(r >= 0.15) & (r < 0.3), 1] = GAP
+    want, steps1 = np_subalignment(g1, ["p0", "p1"], ["s", "t"], g2, pn2, ["u"], pairs)
+    assert np.array_equal(steps1[pairs[:, 0] != np.uint64(GAP)], step[pairs[:, 0] != np.uint64(GAP)])   # shared nodes: path 0's step, not path 1's
+    for part in (steps1[:tile], steps1[tile:]):
+        assert {len(str(s)) for s in part[part >= 0].tolist()} == set(range(1, 8))
+        assert np.any(part < 0)
+    assert -(-n_pairs // 256) == 1028 > 1024
+    got = capi.subalignment_text(gpu_ctx, g1, ["p0", "p1"], ["s", "t"], g2, pn2, ["u"], pairs)
+    if got != want:
+        at = next(i for i, (a, b) in enumerate(zip(got, want)) if a != b) if len(got) == len(want) else min(len(got), len(want))
+        pytest.fail("%d bytes for %d; the first difference at byte %d, line %d" % (len(got), len(want), at, want[:at].count(b"\n")))
+    bad = pairs.copy()
+    bad[262200, 0], bad[262900, 0] = GAP, 7
+    bad[262200, 1] = bad[262900, 1] = len(g2.label) - 1   # crafted_graph leaves its last node on no path
+    with pytest.raises(capi.ClError) as e:
+        capi.subalignment_text(gpu_ctx, g1, ["p0", "p1"], ["s", "t"], g2, pn2, ["u"], bad)
+    assert e.value.code == -1 and "pair 262200 " in str(e.value) and "no path" in str(e.value)
 
 
 def fasta_of(names, seqs):

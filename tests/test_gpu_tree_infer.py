@@ -1,5 +1,7 @@
 """--infer-tree on the device: the k-mer spectra and pair sums of cl_kmer_distances_compute (tree_kernels.hip) against a numpy restatement,
-exactly; the distances against math.log to the bit; the topology of an evolved family; the command line end to end.  CLI runs are fresh
+exactly — up to 200 sequences: more than the 16 384 workgroups of pair_shared_kernel have tiles, so its loop over the tiles runs again, and
+k = 31, 30, 29 and 11 form spectra groups of 4, 16, 64 and 200 sequences, the last two with more than one workgroup of seq_bounds_kernel —;
+the distances against math.log to the bit; the topology of an evolved family; the command line end to end.  CLI runs are fresh
 child processes with their own time limits, one at a time; after a child that ends by a signal or times out none is started."""
 import math
 import os
@@ -133,6 +135,49 @@ def test_gpu_shared_keys_across_tile_edges(gpu_ctx, k):
     spec = check(gpu_ctx, seqs, k)
     assert any(len(spec[i][0]) % PAIR_TILE == 0 for i in range(len(seqs)))
     assert sum(straddles(spec[i], spec[j]) for i in range(len(seqs)) for j in range(i + 1, len(seqs))) > 0
+
+
+@pytest.fixture(scope="module")
+def family200():
+    return family200_sequences()
+
+
+def family200_sequences():
+    """200 sequences: mutated copies of 100 to 400 bases of one 300-base ancestor; an empty one, one shorter than any k of the test and one of
+    N only at 0, 3, 4, 15, 16, 63, 64 and 199 — the first and last places of the spectra groups of k = 31 (4 sequences), 30 (16) and 29 (64)
+    —; and a 20 kbp sequence at 1 and at 198, whose pairs have ten and twenty tiles where the others have one"""
+    rng = random.Random(200)
+    anc = [rng.choice("ACGT") for _ in range(300)]
+    seqs = []
+    for _ in range(200):
+        s = [c if rng.random() > 0.05 else rng.choice("ACGT") for c in anc]
+        n = rng.randrange(100, 401)
+        seqs.append("".join(s[:n] + [rng.choice("ACGT") for _ in range(n - 300)]))
+    for i, s in zip((0, 3, 4, 15, 16, 63, 64, 199), ("", "ACGTA", "N" * 150, "ACGTACGTAC", "", "N" * 40, "ACG", "")):
+        seqs[i] = s
+    for i in (1, 198):
+        seqs[i] = "".join(rng.choice("ACGT") for _ in range(20000))
+    return seqs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [11, 29, 30, 31])
+def test_gpu_more_tiles_than_workgroups_and_every_group_size(gpu_ctx, family200, k):
+    """19 900 pairs, more than 16 384 of them with a tile: pair_shared_kernel's workgroups go round their loop again, reusing sb, split and
+    part, early and late ones with a many-tile pair among one-tile pairs.  k = 31, 30 and 29 form groups of 4, 16 and 64 sequences — the
+    sequences without a k-mer are the first or last of a group —, k = 11 one group of 200: seq_bounds_kernel runs two and four workgroups"""
+    spec = check(gpu_ctx, family200, k)
+    sizes = np.array([len(keys) for keys, _ in spec])
+    assert np.count_nonzero(sizes) == 192
+    both = np.triu(np.outer(sizes > 0, sizes > 0), 1)
+    tiles = -(-(sizes[:, None] + sizes[None, :]) // PAIR_TILE)
+    assert int(both.sum()) == 18336 and int(tiles[both].sum()) > 16384
+    assert int(tiles[1, 198]) >= 10 and int(tiles[1, 5]) >= 5 and int(tiles[5, 150]) == 1
+    if k == 29:
+        together = capi.kmer_distances(gpu_ctx, family200, k=k)
+        for a, b in ((1, 198), (5, 150)):
+            alone = capi.kmer_distances(gpu_ctx, [family200[a], family200[b]], k=k)
+            assert int(alone[1][0, 1]) == int(together[1][a, b]) and alone[0].tolist() == [int(together[0][a]), int(together[0][b])]
 
 
 def evolve_family(seed=3, length=100000):
