@@ -1123,6 +1123,101 @@ def kmer_distances(ctx, sequences, k=21, want_times=False):
     return (total, shared, distance, times) if want_times else (total, shared, distance)
 
 
+class DotplotParams(C.Structure):
+    """cl_dotplot_params"""
+    _fields_ = [("k", C.c_int), ("window", C.c_uint32), ("pairs", C.c_int), ("min_identity", C.c_double), ("tile_windows", C.c_uint32)]
+
+
+class DotplotEntry(C.Structure):
+    """cl_dotplot_entry"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("shared", C.c_uint32), ("denom", C.c_uint32)]
+
+
+class DotplotC(C.Structure):
+    """cl_dotplot"""
+    _fields_ = [("n_seq", C.c_uint64), ("n_windows", C.c_uint64), ("k", C.c_int), ("window", C.c_uint32), ("threshold_q", C.c_uint64),
+                ("win_off", C.POINTER(C.c_uint64)), ("distinct", C.POINTER(C.c_uint32)), ("n_entries", C.c_uint64), ("entries", C.POINTER(DotplotEntry)),
+                ("identity", C.POINTER(C.c_double)), ("spectra_ms", C.c_float), ("pairs_ms", C.c_float)]
+
+
+DOTPLOT_ENTRY = np.dtype([("a", np.uint32), ("b", np.uint32), ("shared", np.uint32), ("denom", np.uint32)])
+DOTPLOT_PAIRS = {"all": 0, "self": 1}
+
+
+def _dotplot(ctx, sequences, k, window, pairs, min_identity, tile_windows, names):
+    lib = load_library()
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+    n = len(raw)
+    bufs = (C.c_char_p * max(n, 1))(*raw)
+    lens = np.array([len(s) for s in raw], dtype=np.uint64)
+    lib.cl_dotplot_params_default.argtypes = [C.POINTER(DotplotParams)]
+    lib.cl_dotplot_params_default.restype = None
+    lib.cl_dotplot_free.argtypes = [C.POINTER(DotplotC)]
+    lib.cl_dotplot_free.restype = None
+    params = DotplotParams()
+    lib.cl_dotplot_params_default(C.byref(params))
+    if k is not None:
+        params.k = int(k)
+    if window is not None:
+        params.window = int(window)
+    if pairs is not None:
+        params.pairs = DOTPLOT_PAIRS.get(pairs, pairs)
+    if min_identity is not None:
+        params.min_identity = float(min_identity)
+    if tile_windows is not None:
+        params.tile_windows = int(tile_windows)
+    out = DotplotC()
+    if ctx is None:
+        h = None
+        lib.cl_kmer_dotplot_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DotplotParams), C.POINTER(DotplotC)]
+        rc = lib.cl_kmer_dotplot_host(bufs, lens.ctypes.data, n, C.byref(params), C.byref(out))
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_kmer_dotplot_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DotplotParams), C.POINTER(DotplotC)]
+        rc = lib.cl_kmer_dotplot_compute(h, bufs, lens.ctypes.data, n, C.byref(params), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        G, E = int(out.n_windows), int(out.n_entries)
+        res = {"n_seq": int(out.n_seq), "n_windows": G, "k": int(out.k), "window": int(out.window), "threshold_q": int(out.threshold_q),
+               "win_off": np.ctypeslib.as_array(out.win_off, shape=(n + 1,)).copy(),
+               "distinct": np.ctypeslib.as_array(out.distinct, shape=(G,)).copy() if G else np.zeros(0, np.uint32),
+               "entries": np.frombuffer(C.string_at(out.entries, 16 * E), dtype=DOTPLOT_ENTRY).copy() if E else np.zeros(0, DOTPLOT_ENTRY),
+               "identity": np.ctypeslib.as_array(out.identity, shape=(E,)).copy() if E else np.zeros(0, np.float64),
+               "spectra_ms": float(out.spectra_ms), "pairs_ms": float(out.pairs_ms)}
+        if names is not None:
+            if len(names) != n:
+                raise ValueError("%d names for %d sequences" % (len(names), n))
+            arr = (C.c_char_p * max(n, 1))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names])
+            lib.cl_dotplot_tsv.argtypes = [C.POINTER(DotplotC), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+            text, ln = C.c_void_p(), C.c_uint64()
+            rc = lib.cl_dotplot_tsv(C.byref(out), arr, lens.ctypes.data, C.byref(text), C.byref(ln))
+            if rc != 0:
+                _raise_last(lib, rc)
+            try:
+                res["tsv"] = C.string_at(text.value, ln.value)
+            finally:
+                _libc_free(text)
+        return res
+    finally:
+        lib.cl_dotplot_free(C.byref(out))
+
+
+def kmer_dotplot_host(sequences, k=None, window=None, pairs=None, min_identity=None, tile_windows=None, names=None):
+    """cl_kmer_dotplot_host (host only, the definition): the windowed k-mer identity map of `sequences` (str or bytes) as a dict of n_seq,
+    n_windows, k, window, threshold_q, win_off [n + 1] uint64, distinct [n_windows] uint32, entries [n_entries] of DOTPLOT_ENTRY in ascending
+    (a, b) order, identity [n_entries] float64 and the two device times (0 here).  None: the value of cl_dotplot_params_default (k 21, window
+    2000, all pairs, 86 %); pairs: "all" / "self" or 0 / 1.  With names, "tsv" holds the rows of cl_dotplot_tsv as bytes"""
+    return _dotplot(None, sequences, k, window, pairs, min_identity, tile_windows, names)
+
+
+def kmer_dotplot(ctx, sequences, k=None, window=None, pairs=None, min_identity=None, tile_windows=None, names=None):
+    """cl_kmer_dotplot_compute: the same on the device, byte for byte; tile_windows forces the windows a tile of the pair kernel holds per side"""
+    if ctx is None:
+        raise ValueError("kmer_dotplot needs a context (kmer_dotplot_host is the host call)")
+    return _dotplot(ctx, sequences, k, window, pairs, min_identity, tile_windows, names)
+
+
 def neighbor_joining_newick(distance, names):
     """cl_neighbor_joining_newick (host only): the midpoint-rooted neighbor-joining tree of an [n, n] distance matrix as Newick text"""
     lib = load_library()
@@ -1447,7 +1542,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 20    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 21    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -1690,6 +1785,7 @@ EXPORTED_SYMBOLS = [
     "cl_induced_pairwise_profile", "cl_induced_pairwise_profiles", "cl_induced_gap_events", "cl_induced_gap_events_batch",
     "cl_induced_pairwise_agreement", "cl_induced_pairwise_agreements",
     "cl_msa_columns_params_default", "cl_msa_column_layout", "cl_msa_columns_host", "cl_msa_columns_compute", "cl_msa_columns_free", "cl_msa_columns_layout_seconds",
+    "cl_dotplot_params_default", "cl_kmer_dotplot_host", "cl_kmer_dotplot_compute", "cl_dotplot_tsv", "cl_dotplot_free",
 ]
 
 

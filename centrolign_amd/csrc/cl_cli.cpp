@@ -15,11 +15,14 @@
 //     baseline graph of the same sequences (cl_induced_pairwise_agreements); --graph GFA compares a graph that is already there instead of aligning;
 //   - --msa-out, --column-stats and --variable-sites write the alignment as columns: aligned FASTA, a record per column, and the aligned FASTA of
 //     the variable sites alone (cl_msa_columns_compute on the printed graph; --msa-layout, --site-min-minor, --site-max-gaps); not with -c;
+//   - --dotplot FILE writes the windowed k-mer identity map of the input sequences (cl_kmer_dotplot_compute; --dotplot-k, --dotplot-window,
+//     --dotplot-min-identity, --dotplot-pairs) before the alignment starts; --dotplot-only ends the run there;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -399,6 +402,35 @@ bool write_pair_agreement(cl_context* ctx, const NamedGraph& printed, const Name
     return true;
 }
 
+// --dotplot: the windowed k-mer identity map of the FASTA's sequences, named as --pair-stats names them
+bool write_dotplot(cl_context* ctx, const std::string& fasta_text, const cl_dotplot_params& params, const std::string& file, std::string& err) {
+    cl_fasta fa;
+    if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) { err = lib_error(); return false; }
+    struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
+    std::vector<std::string> shown(fa.names, fa.names + fa.n_sequences);
+    std::vector<const char*> names;
+    for (std::string& nm : shown) { std::replace(nm.begin(), nm.end(), '/', '_'); names.push_back(nm.c_str()); }
+    cl_dotplot plot;
+    if (cl_kmer_dotplot_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, &params, &plot)) {
+        const char* e = cl_last_error(ctx);
+        err = std::string("the dot plot: ") + (e && *e ? e : "failed");
+        return false;
+    }
+    struct FreePlot { cl_dotplot* d; ~FreePlot() { cl_dotplot_free(d); } } free_plot{&plot};
+    char line[256];
+    snprintf(line, sizeof(line), "The dot plot: %llu windows of %u bases, %llu entries; k-mer lists %.3f ms, window pairs %.3f ms on the device.",
+             (unsigned long long)plot.n_windows, plot.window, (unsigned long long)plot.n_entries, plot.spectra_ms, plot.pairs_ms);
+    log_line(LOG_VERBOSE, line);
+    char* text = nullptr;
+    uint64_t len = 0;
+    if (cl_dotplot_tsv(&plot, names.data(), fa.lengths, &text, &len)) { err = "the dot plot: " + lib_error(); return false; }
+    FILE* f = fopen(file.c_str(), "wb");
+    const bool written = f && fwrite(text, 1, len, f) == len;
+    free(text);
+    if ((f && fclose(f) != 0) || !written) { err = "could not write the dot plot to " + file; return false; }
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -446,12 +478,19 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --msa-layout WORD           With the three above, the columns: level (compact, bubble branches side by side) or node (one graph node per column) [level]\n");
     fprintf(o, " --site-min-minor INT        A column is a variable site if its second most frequent base occurs at least INT times [1]\n");
     fprintf(o, " --site-max-gaps INT         ... and it has at most INT gaps [no limit]\n");
+    fprintf(o, " --dotplot FILE              Write the windowed k-mer identity map (dot plot) of the input sequences, one row per kept window pair, to FILE (which must not exist yet)\n");
+    fprintf(o, " --dotplot-k INT             With --dotplot, the k-mer length, 1 to 31 [21]\n");
+    fprintf(o, " --dotplot-window INT        With --dotplot, the window in bases, k to 1048576 [2000]\n");
+    fprintf(o, " --dotplot-min-identity FLOAT  With --dotplot, keep a window pair from this identity in percent on [86]\n");
+    fprintf(o, " --dotplot-pairs all|self    With --dotplot, compare all windows or only the windows of the same sequence [all]\n");
+    fprintf(o, " --dotplot-only              With --dotplot, end after writing the map: nothing is aligned or printed\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
     fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats, --dist-out, --pair-profile, --window,\n");
     fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement, --graph, --msa-out, --column-stats, --variable-sites, --msa-layout,\n");
-    fprintf(o, "--site-min-minor and --site-max-gaps are added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "--site-min-minor, --site-max-gaps, --dotplot, --dotplot-k, --dotplot-window, --dotplot-min-identity, --dotplot-pairs and --dotplot-only\n");
+    fprintf(o, "are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -477,13 +516,17 @@ int run(int argc, char** argv) {
     std::string msa_out, column_stats, variable_sites, msa_layout_arg, site_min_minor_arg, site_max_gaps_arg;
     bool have_graph = false, have_msa_layout = false, have_site_min_minor = false, have_site_max_gaps = false;
     bool force_gfa_output = false, generate_config = false, infer_tree = false, have_window = false, have_min_event = false;
+    std::string dotplot, dotplot_k_arg, dotplot_window_arg, dotplot_identity_arg, dotplot_pairs_arg;
+    bool have_dotplot_k = false, have_dotplot_window = false, have_dotplot_identity = false, have_dotplot_pairs = false, dotplot_only = false;
+    bool beside_dotplot_only = false;   // an option --dotplot-only does not go with
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
            OPT_PAIR_STATS = 1007, OPT_DIST_OUT = 1008, OPT_REFINE_TREE = 1009,
            OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013,
            OPT_COMPARE_TO = 1014, OPT_PAIR_AGREEMENT = 1015, OPT_GRAPH = 1016,
-           OPT_MSA_OUT = 1017, OPT_COLUMN_STATS = 1018, OPT_VARIABLE_SITES = 1019, OPT_MSA_LAYOUT = 1020, OPT_SITE_MIN_MINOR = 1021, OPT_SITE_MAX_GAPS = 1022 };
+           OPT_MSA_OUT = 1017, OPT_COLUMN_STATS = 1018, OPT_VARIABLE_SITES = 1019, OPT_MSA_LAYOUT = 1020, OPT_SITE_MIN_MINOR = 1021, OPT_SITE_MAX_GAPS = 1022,
+           OPT_DOTPLOT = 1023, OPT_DOTPLOT_K = 1024, OPT_DOTPLOT_WINDOW = 1025, OPT_DOTPLOT_MIN_IDENTITY = 1026, OPT_DOTPLOT_PAIRS = 1027, OPT_DOTPLOT_ONLY = 1028 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -524,6 +567,12 @@ int run(int argc, char** argv) {
         {"msa-layout", required_argument, nullptr, OPT_MSA_LAYOUT},
         {"site-min-minor", required_argument, nullptr, OPT_SITE_MIN_MINOR},
         {"site-max-gaps", required_argument, nullptr, OPT_SITE_MAX_GAPS},
+        {"dotplot", required_argument, nullptr, OPT_DOTPLOT},
+        {"dotplot-k", required_argument, nullptr, OPT_DOTPLOT_K},
+        {"dotplot-window", required_argument, nullptr, OPT_DOTPLOT_WINDOW},
+        {"dotplot-min-identity", required_argument, nullptr, OPT_DOTPLOT_MIN_IDENTITY},
+        {"dotplot-pairs", required_argument, nullptr, OPT_DOTPLOT_PAIRS},
+        {"dotplot-only", no_argument, nullptr, OPT_DOTPLOT_ONLY},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -532,6 +581,7 @@ int run(int argc, char** argv) {
         if (o == -1) break;
         const char* name = nullptr;   // the parameter this option sets from its argument
         const char* value = optarg;
+        if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_DOTPLOT && o <= OPT_DOTPLOT_ONLY)) beside_dotplot_only = true;
         switch (o) {
         case 'T': name = "tree_name"; break;
         case 'A': name = "all_pairs_prefix"; break;
@@ -574,6 +624,12 @@ int run(int argc, char** argv) {
         case OPT_MSA_LAYOUT: msa_layout_arg = optarg; have_msa_layout = true; break;
         case OPT_SITE_MIN_MINOR: site_min_minor_arg = optarg; have_site_min_minor = true; break;
         case OPT_SITE_MAX_GAPS: site_max_gaps_arg = optarg; have_site_max_gaps = true; break;
+        case OPT_DOTPLOT: dotplot = optarg; break;
+        case OPT_DOTPLOT_K: dotplot_k_arg = optarg; have_dotplot_k = true; break;
+        case OPT_DOTPLOT_WINDOW: dotplot_window_arg = optarg; have_dotplot_window = true; break;
+        case OPT_DOTPLOT_MIN_IDENTITY: dotplot_identity_arg = optarg; have_dotplot_identity = true; break;
+        case OPT_DOTPLOT_PAIRS: dotplot_pairs_arg = optarg; have_dotplot_pairs = true; break;
+        case OPT_DOTPLOT_ONLY: dotplot_only = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -615,6 +671,8 @@ int run(int argc, char** argv) {
             return fail("--graph cannot be combined with another output option (--msa-out, --column-stats, --variable-sites)");
     }
 
+    if (dotplot_only && !dotplot.empty() && beside_dotplot_only)
+        return fail("--dotplot-only goes with the --dotplot options, -v and --devices alone: nothing else is run");
     if (!config_name.empty()) {
         if (generate(cfg) != generate(own.defaults))
             fprintf(stderr, "warning: All other command-line arguments are being overridden by config file parameters.\n\n");
@@ -626,6 +684,41 @@ int run(int argc, char** argv) {
         cfg = own.cfg = parsed;
     }
 
+    // --dotplot and its options, checked before anything is read or opened
+    cl_dotplot_params dotplot_params;
+    cl_dotplot_params_default(&dotplot_params);
+    if (dotplot.empty()) {
+        const char* lone = have_dotplot_k ? "--dotplot-k" : have_dotplot_window ? "--dotplot-window" : have_dotplot_identity ? "--dotplot-min-identity"
+                           : have_dotplot_pairs ? "--dotplot-pairs" : dotplot_only ? "--dotplot-only" : nullptr;
+        if (lone) return fail(std::string(lone) + " needs --dotplot");
+    } else {
+        if (have_graph) return fail("--dotplot cannot be combined with --graph: it reads the sequences of a FASTA");
+        uint64_t v = 0;
+        if (have_dotplot_k && (!parse_positive(dotplot_k_arg, v) || v > 31)) return fail("--dotplot-k expects a k-mer length from 1 to 31, got '" + dotplot_k_arg + "'");
+        if (have_dotplot_k) dotplot_params.k = (int)v;
+        if (have_dotplot_window && (!parse_positive(dotplot_window_arg, v) || v > (1u << 20) || v < (uint64_t)dotplot_params.k))
+            return fail("--dotplot-window expects a whole number of bases from k = " + std::to_string(dotplot_params.k) + " to 1048576, got '" + dotplot_window_arg + "'");
+        if (have_dotplot_window) dotplot_params.window = (uint32_t)v;
+        if (dotplot_params.window < (uint32_t)dotplot_params.k) return fail("--dotplot-k " + dotplot_k_arg + " is more than the window of " + std::to_string(dotplot_params.window) + " bases");
+        if (have_dotplot_identity) {
+            char* end = nullptr;
+            errno = 0;
+            const double x = strtod(dotplot_identity_arg.c_str(), &end);
+            if (dotplot_identity_arg.empty() || *end || errno || !(x >= 0.0 && x <= 100.0))
+                return fail("--dotplot-min-identity expects a percentage from 0 to 100, got '" + dotplot_identity_arg + "'");
+            dotplot_params.min_identity = x;
+        }
+        if (have_dotplot_pairs) {
+            if (dotplot_pairs_arg == "all") dotplot_params.pairs = 0;
+            else if (dotplot_pairs_arg == "self") dotplot_params.pairs = 1;
+            else return fail("--dotplot-pairs expects all or self, got '" + dotplot_pairs_arg + "'");
+        }
+        if (std::ifstream(dotplot).good()) return fail("Dot plot file already exists: " + dotplot);
+        const std::string others[10] = {tree_out, pair_stats, dist_out, pair_profile, pair_events, pair_agreement, msa_out, column_stats, variable_sites,
+                                        config_value(cfg, "subalignments_filepath")};
+        for (const std::string& other : others)
+            if (dotplot == other) return fail("--dotplot names the file of another output option");
+    }
     // the tree options of this project, checked before anything is read or opened
     if (infer_tree && !config_value(cfg, "tree_name").empty()) return fail("--infer-tree cannot be combined with a guide tree (-T or tree_name)");
     if (!tree_out.empty() && !infer_tree && refine_arg.empty()) return fail("--tree-out needs --infer-tree");
@@ -747,7 +840,18 @@ int run(int argc, char** argv) {
     if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) return fail(lib_error());
     const uint64_t n_sequences = fa.n_sequences;
     const std::vector<std::string> sequence_names(fa.names, fa.names + fa.n_sequences);
+    uint64_t n_bases = 0;
+    for (uint64_t i = 0; i < fa.n_sequences; ++i) n_bases += fa.lengths[i];
     cl_fasta_free(&fa);
+    if (!dotplot.empty() && n_bases >= (1ull << 30)) return fail("--dotplot takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
+    if (dotplot_only) {   // no alignment, nothing on standard output
+        if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
+        own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
+        if (!own.ctx) return fail("no usable GPU: " + lib_error());
+        if (!write_dotplot(own.ctx, fasta_text, dotplot_params, dotplot, err)) return fail(err);
+        log_line(LOG_MINIMAL, "Wrote the dot plot to " + dotplot + ", exiting.");
+        return 0;
+    }
     if (n_sequences < 2)
         return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains " + std::to_string(n_sequences) +
                     " sequence(s), cannot form an alignment");
@@ -784,6 +888,10 @@ int run(int argc, char** argv) {
     own.ctx = cl_context_create(device);
     if (!own.ctx) return fail("no usable GPU: " + lib_error());
 
+    if (!dotplot.empty()) {
+        log_line(LOG_BASIC, "Writing the dot plot.");
+        if (!write_dotplot(own.ctx, fasta_text, dotplot_params, dotplot, err)) return fail(err);
+    }
     if (infer_tree) {   // the tree goes to cl_msa exactly as the text of a -T file would
         log_line(LOG_BASIC, "Inferring a guide tree from k-mer distances.");
         const auto t0 = std::chrono::steady_clock::now();

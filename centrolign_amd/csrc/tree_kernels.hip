@@ -22,22 +22,13 @@
 
 #include "cl_internal.hpp"
 #include "cl_radix.h"
+#include "kmer_code.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kPairTile = 2048;       // merged items per pair tile ("Guide tree inference"; tests/test_gpu_tree_infer.py aims at it)
 constexpr uint64_t kGroupText = 1ull << 30; // text positions per spectra group (beyond that a sequence forms a group of its own)
-
-__device__ __forceinline__ uint32_t base_code(uint8_t c) {   // encode_base for ACGTacgt, 4: not a k-mer character
-    switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return 4;
-    }
-}
 
 // position p of the group's text: key = (sequence in group) << 2k | k-mer; flag = the window [p, p + k) lies in one sequence and holds only ACGTacgt
 __global__ void __launch_bounds__(kBlock) kmer_keys_kernel(const uint8_t* __restrict__ text, uint32_t n_text, const uint64_t* __restrict__ seq_start,
@@ -178,12 +169,6 @@ __global__ void __launch_bounds__(kBlock) pair_shared_kernel(const uint64_t* __r
         }
         __syncthreads();   // (sb, split and part are reused by the next tile)
     }
-}
-
-uint32_t bits_for(uint64_t v) {   // bits needed to hold values 0 .. v (0 for v = 0)
-    uint32_t b = 0;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
 }
 
 }  // namespace

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 20 /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 21 /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -1029,6 +1029,61 @@ int  cl_alignment_distances(const cl_pair_stats* stats /* [n*(n-1)/2] */, uint64
 int  cl_refine_guide_tree(cl_context* ctx, const char* fasta_text, uint64_t fasta_len, const char* newick /* NULL: in-order */, const cl_msa_params* params,
                           int max_rounds, char** newick_out, uint64_t* len_out /* may be NULL */, int* rounds_run_out /* may be NULL */,
                           int* converged_out /* may be NULL */);
+
+/* --- windowed k-mer identity maps, "dot plots" (the CLI's --dotplot; the reference has none) -----------------------------------------------------
+ * The first view of a set of centromeric arrays, as ModDotPlot and StainedGlass draw it: every sequence cut into windows, and for every pair of
+ * windows the share of k-mers they have in common.  Every number is exact.
+ * Windows.  Sequences are numbered s = 0 .. n-1 in the order given, L_s their lengths.  Window w of s covers positions [w W, min((w + 1) W, L_s));
+ *   s has ceil(L_s / W) windows, an empty sequence none.  The global window index is g = win_off[s] + w; win_off[n] = n_windows = G.
+ * k-mers.  A run of k characters, all from ACGTacgt, coded as in cl_kmer_distances_compute (forward strand, first base most significant); a run
+ *   holding any other character is none.  A k-mer belongs to the window its FIRST base stands in: it may reach up to k - 1 bases into the next
+ *   window of the same sequence, never past the sequence's end.  K_g = the set of distinct k-mers of window g, distinct[g] = |K_g|.
+ * Pairs.  For a <= b: shared = |K_a n K_b|, denom = min(distinct[a], distinct[b]); the pair is kept iff shared >= 1 and
+ *   shared * 2^32 >= q * denom with q = (uint64) ceil(ldexp(pow(min_identity / 100, k), 32)), computed once on the host in doubles and returned
+ *   as threshold_q (the test itself is integer only).  min_identity 0: q = 0, every pair that shares a k-mer; 100: q = 2^32, only
+ *   shared == denom.  The diagonal a = b is kept whenever distinct[a] > 0.  pairs = 0 considers every a <= b, pairs = 1 only windows of the
+ *   same sequence.
+ * Output.  The kept pairs as 16-byte entries {a, b, shared, denom} in strictly ascending (a, b) order; order and bytes do not depend on
+ *   scheduling, tile size or device.  identity[e] = 100.0 * pow((double)shared / (double)denom, 1.0 / k), computed on the host without fused
+ *   multiply-adds.
+ * Limits.  k in 1..31; k <= window <= 2^20 (so shared * 2^32 stays below 2^52); n >= 1; 0 <= min_identity <= 100 and finite; pairs 0 or 1;
+ *   the lengths add up to less than 2^30 (the 32-bit counts of the device sort); G < 2^32; tile_windows <= 64.  Anything else is
+ *   CL_ERR_INVALID_ARGUMENT with a cl_last_error that names the argument.
+ * cl_kmer_dotplot_host: the definition, written plainly on the host (sorted vectors, std::set_intersection); no context, no GPU.
+ * cl_kmer_dotplot_compute: the device path (dotplot_kernels.hip) with the same bytes in every field but the two times.  tile_windows = 0 lets
+ *   the library choose how many windows a tile of the pair kernel holds per side, any other value forces it; the result does not depend on it.
+ *   The G x G matrix is never formed.  spectra_ms / pairs_ms: device time of the two phases by events (0 from the host call).
+ * cl_dotplot_tsv: host only.  One row per entry, in entry order: sample1 start1 end1 sample2 start2 end2 shared distinct1 distinct2 identity,
+ *   tab-separated under a header line of these words; coordinates 0-based and half-open, the end clipped to the sequence's length; identity as
+ *   %.9g; every line ends with a line end.  This is the BEDPE layout ModDotPlot's plotting scripts read, with three count columns in front of
+ *   the identity.  names[s] is written as given.  Text returned through char** is malloc'ed.
+ * The arrays of a cl_dotplot are malloc'ed: release them with cl_dotplot_free. */
+typedef struct cl_dotplot_params {
+    int      k;              /* 21 */
+    uint32_t window;         /* 2000 */
+    int      pairs;          /* 0: all window pairs, 1: pairs of windows of the same sequence */
+    double   min_identity;   /* 86.0, in percent */
+    uint32_t tile_windows;   /* 0: the library chooses; 1..64: windows per side of a pair tile (tests put tile edges inside tiny inputs with it) */
+} cl_dotplot_params;
+typedef struct cl_dotplot_entry { uint32_t a, b, shared, denom; } cl_dotplot_entry;   /* 16 bytes */
+typedef struct cl_dotplot {
+    uint64_t  n_seq, n_windows;
+    int       k;
+    uint32_t  window;
+    uint64_t  threshold_q;
+    uint64_t* win_off;    /* [n_seq + 1] */
+    uint32_t* distinct;   /* [n_windows] */
+    uint64_t  n_entries;
+    cl_dotplot_entry* entries;   /* [n_entries] */
+    double*   identity;          /* [n_entries] */
+    float     spectra_ms, pairs_ms;   /* device time by events */
+} cl_dotplot;
+void cl_dotplot_params_default(cl_dotplot_params* params);
+int  cl_kmer_dotplot_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_dotplot_params* params, cl_dotplot* out);
+int  cl_kmer_dotplot_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_dotplot_params* params,
+                             cl_dotplot* out);
+int  cl_dotplot_tsv(const cl_dotplot* plot, const char* const* names, const uint64_t* lengths, char** text_out, uint64_t* len_out /* may be NULL */);
+void cl_dotplot_free(cl_dotplot* out);
 
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
