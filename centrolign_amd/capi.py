@@ -1218,6 +1218,151 @@ def kmer_dotplot(ctx, sequences, k=None, window=None, pairs=None, min_identity=N
     return _dotplot(ctx, sequences, k, window, pairs, min_identity, tile_windows, names)
 
 
+class PeriodsParams(C.Structure):
+    """cl_periods_params"""
+    _fields_ = [("k", C.c_int), ("window", C.c_uint32), ("max_period", C.c_uint32), ("n_peaks", C.c_uint32), ("peak_radius", C.c_uint32),
+                ("min_period", C.c_uint32), ("min_count", C.c_uint32), ("want_hist", C.c_int)]
+
+
+class PeriodPeak(C.Structure):
+    """cl_period_peak"""
+    _fields_ = [("period", C.c_uint32), ("count", C.c_uint32)]
+
+
+class PeriodSpectrumC(C.Structure):
+    """cl_period_spectrum"""
+    _fields_ = [("n_seq", C.c_uint64), ("n_windows", C.c_uint64), ("n_rows", C.c_uint64), ("k", C.c_int), ("window", C.c_uint32), ("max_period", C.c_uint32),
+                ("n_peaks", C.c_uint32), ("win_off", C.POINTER(C.c_uint64)), ("kmers", C.POINTER(C.c_uint32)), ("links", C.POINTER(C.c_uint32)),
+                ("far", C.POINTER(C.c_uint32)), ("last", C.POINTER(C.c_uint32)), ("peaks", C.POINTER(PeriodPeak)), ("hist", C.POINTER(C.c_uint32)),
+                ("links_ms", C.c_float), ("hist_ms", C.c_float)]
+
+
+PERIOD_PEAK = np.dtype([("period", np.uint32), ("count", np.uint32)])
+PERIODS_SCOPE = {"both": 0, "sequences": 1, "windows": 2}
+_PERIODS_FIELDS = ("k", "window", "max_period", "n_peaks", "peak_radius", "min_period", "min_count", "want_hist")
+_PERIODS_COUNTERS = ("kmers", "links", "far", "last")
+
+
+def _periods_params(lib, params):
+    lib.cl_periods_params_default.argtypes = [C.POINTER(PeriodsParams)]
+    lib.cl_periods_params_default.restype = None
+    p = PeriodsParams()
+    lib.cl_periods_params_default(C.byref(p))
+    for name, v in params.items():
+        if name not in _PERIODS_FIELDS:
+            raise TypeError("no period parameter named %r" % name)
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def _period_spectrum(ctx, sequences, params):
+    lib = load_library()
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+    n = len(raw)
+    bufs = (C.c_char_p * max(n, 1))(*raw)
+    lens = np.array([len(s) for s in raw], dtype=np.uint64)
+    p = _periods_params(lib, params)
+    lib.cl_period_spectrum_free.argtypes = [C.POINTER(PeriodSpectrumC)]
+    lib.cl_period_spectrum_free.restype = None
+    out = PeriodSpectrumC()
+    if ctx is None:
+        h = None
+        lib.cl_period_spectrum_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PeriodsParams), C.POINTER(PeriodSpectrumC)]
+        rc = lib.cl_period_spectrum_host(bufs, lens.ctypes.data, n, C.byref(p), C.byref(out))
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_period_spectrum_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PeriodsParams), C.POINTER(PeriodSpectrumC)]
+        rc = lib.cl_period_spectrum_compute(h, bufs, lens.ctypes.data, n, C.byref(p), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        R, D, P = int(out.n_rows), int(out.max_period), int(out.n_peaks)
+        res = {"n_seq": int(out.n_seq), "n_windows": int(out.n_windows), "n_rows": R, "k": int(out.k), "window": int(out.window), "max_period": D, "n_peaks": P,
+               "win_off": np.ctypeslib.as_array(out.win_off, shape=(n + 1,)).copy(),
+               "peaks": np.frombuffer(C.string_at(out.peaks, 8 * R * P), dtype=PERIOD_PEAK).copy().reshape(R, P),
+               "hist": np.ctypeslib.as_array(out.hist, shape=(R * (D + 1),)).copy().reshape(R, D + 1) if out.hist else None,
+               "links_ms": float(out.links_ms), "hist_ms": float(out.hist_ms)}
+        for name in _PERIODS_COUNTERS:
+            res[name] = np.ctypeslib.as_array(getattr(out, name), shape=(R,)).copy()
+        return res
+    finally:
+        lib.cl_period_spectrum_free(C.byref(out))
+
+
+def period_spectrum_host(sequences, **params):
+    """cl_period_spectrum_host (host only, the definition): the repeat period spectra of `sequences` (str or bytes) as a dict of n_seq, n_windows,
+    n_rows = R, k, window, max_period = D, n_peaks = P, win_off [n + 1] uint64, kmers / links / far / last [R] uint32, peaks [R, P] of PERIOD_PEAK,
+    hist [R, D + 1] uint32 (None with want_hist=0) and the two device times (0 here).  params: the fields of cl_periods_params; one left out or
+    None keeps the value of cl_periods_params_default (k 8, window 10000, max_period 8000, n_peaks 3, peak_radius 1, min_period 1, min_count 2,
+    want_hist 1)"""
+    return _period_spectrum(None, sequences, params)
+
+
+def period_spectrum(ctx, sequences, **params):
+    """cl_period_spectrum_compute: the same on the device, byte for byte"""
+    if ctx is None:
+        raise ValueError("period_spectrum needs a context (period_spectrum_host is the host call)")
+    return _period_spectrum(ctx, sequences, params)
+
+
+def period_peaks_host(row, **params):
+    """cl_period_peaks_host: the peaks [n_peaks] of PERIOD_PEAK of one row of max_period + 1 bins (bin 0 is ignored) under n_peaks, peak_radius,
+    min_period and min_count of params"""
+    lib = load_library()
+    h = np.ascontiguousarray(row, dtype=np.uint32)
+    if h.ndim != 1 or len(h) < 2:
+        raise ValueError("a row has max_period + 1 >= 2 bins")
+    p = _periods_params(lib, params)
+    out = np.zeros(min(max(int(p.n_peaks), 1), 16), PERIOD_PEAK)   # (an n_peaks out of range is refused before anything is written)
+    lib.cl_period_peaks_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PeriodsParams), C.c_void_p]
+    rc = lib.cl_period_peaks_host(h.ctypes.data, len(h) - 1, C.byref(p), out.ctypes.data)
+    if rc != 0:
+        _raise_last(lib, rc)
+    return out
+
+
+def _periods_text(fn_name, spectrum, names, lengths, scope):
+    lib = load_library()
+    n, R, D, P = spectrum["n_seq"], spectrum["n_rows"], spectrum["max_period"], spectrum["n_peaks"]
+    if len(names) != n or len(lengths) != n:
+        raise ValueError("%d names and %d lengths for %d sequences" % (len(names), len(lengths), n))
+    keep = {name: np.ascontiguousarray(spectrum[name], dtype=np.uint32) for name in _PERIODS_COUNTERS}
+    keep["win_off"] = np.ascontiguousarray(spectrum["win_off"], dtype=np.uint64)
+    keep["peaks"] = np.ascontiguousarray(spectrum["peaks"], dtype=PERIOD_PEAK)
+    keep["hist"] = None if spectrum["hist"] is None else np.ascontiguousarray(spectrum["hist"], dtype=np.uint32)
+    assert keep["peaks"].shape == (R, P) and (keep["hist"] is None or keep["hist"].shape == (R, D + 1))
+    sp = PeriodSpectrumC(n_seq=n, n_windows=spectrum["n_windows"], n_rows=R, k=spectrum["k"], window=spectrum["window"], max_period=D, n_peaks=P)
+    sp.win_off = keep["win_off"].ctypes.data_as(C.POINTER(C.c_uint64))
+    for name in _PERIODS_COUNTERS:
+        setattr(sp, name, keep[name].ctypes.data_as(C.POINTER(C.c_uint32)))
+    sp.peaks = keep["peaks"].ctypes.data_as(C.POINTER(PeriodPeak))
+    if keep["hist"] is not None:
+        sp.hist = keep["hist"].ctypes.data_as(C.POINTER(C.c_uint32))
+    arr = (C.c_char_p * max(n, 1))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names])
+    lens = np.array([int(x) for x in lengths], dtype=np.uint64)
+    fn = getattr(lib, fn_name)
+    fn.argtypes = [C.POINTER(PeriodSpectrumC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = fn(C.byref(sp), arr, lens.ctypes.data, PERIODS_SCOPE.get(scope, scope), C.byref(text), C.byref(ln))
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return C.string_at(text.value, ln.value)
+    finally:
+        _libc_free(text)
+
+
+def periods_tsv(spectrum, names, lengths, scope="both"):
+    """cl_periods_tsv (host only): the peak rows of a period_spectrum dict as bytes; scope "both" / "sequences" / "windows" or 0 / 1 / 2"""
+    return _periods_text("cl_periods_tsv", spectrum, names, lengths, scope)
+
+
+def periods_hist_tsv(spectrum, names, lengths, scope="both"):
+    """cl_periods_hist_tsv (host only): the non-zero bins 1..D of the same rows; a spectrum without hist is an error"""
+    return _periods_text("cl_periods_hist_tsv", spectrum, names, lengths, scope)
+
+
 def neighbor_joining_newick(distance, names):
     """cl_neighbor_joining_newick (host only): the midpoint-rooted neighbor-joining tree of an [n, n] distance matrix as Newick text"""
     lib = load_library()
@@ -1786,6 +1931,8 @@ EXPORTED_SYMBOLS = [
     "cl_induced_pairwise_agreement", "cl_induced_pairwise_agreements",
     "cl_msa_columns_params_default", "cl_msa_column_layout", "cl_msa_columns_host", "cl_msa_columns_compute", "cl_msa_columns_free", "cl_msa_columns_layout_seconds",
     "cl_dotplot_params_default", "cl_kmer_dotplot_host", "cl_kmer_dotplot_compute", "cl_dotplot_tsv", "cl_dotplot_free",
+    "cl_periods_params_default", "cl_period_spectrum_host", "cl_period_spectrum_compute", "cl_period_peaks_host", "cl_periods_tsv", "cl_periods_hist_tsv",
+    "cl_period_spectrum_free",
 ]
 
 

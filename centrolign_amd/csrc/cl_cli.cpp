@@ -17,6 +17,8 @@
 //     the variable sites alone (cl_msa_columns_compute on the printed graph; --msa-layout, --site-min-minor, --site-max-gaps); not with -c;
 //   - --dotplot FILE writes the windowed k-mer identity map of the input sequences (cl_kmer_dotplot_compute; --dotplot-k, --dotplot-window,
 //     --dotplot-min-identity, --dotplot-pairs) before the alignment starts; --dotplot-only ends the run there;
+//   - --periods FILE writes the repeat period spectra of the input sequences (cl_period_spectrum_compute; --periods-hist and the --periods-*
+//     options) before the alignment starts; --periods-only ends the run there;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -431,6 +433,42 @@ bool write_dotplot(cl_context* ctx, const std::string& fasta_text, const cl_dotp
     return true;
 }
 
+// --periods / --periods-hist: the repeat period spectra of the FASTA's sequences, named as --pair-stats names them
+bool write_periods(cl_context* ctx, const std::string& fasta_text, const cl_periods_params& params, int scope, const std::string& file, const std::string& hist_file,
+                   std::string& err) {
+    cl_fasta fa;
+    if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) { err = lib_error(); return false; }
+    struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
+    std::vector<std::string> shown(fa.names, fa.names + fa.n_sequences);
+    std::vector<const char*> names;
+    for (std::string& nm : shown) { std::replace(nm.begin(), nm.end(), '/', '_'); names.push_back(nm.c_str()); }
+    cl_period_spectrum spec;
+    if (cl_period_spectrum_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, &params, &spec)) {
+        const char* e = cl_last_error(ctx);
+        err = std::string("the period spectra: ") + (e && *e ? e : "failed");
+        return false;
+    }
+    struct FreeSpectrum { cl_period_spectrum* d; ~FreeSpectrum() { cl_period_spectrum_free(d); } } free_spectrum{&spec};
+    uint64_t n_links = 0;
+    for (uint64_t s = 0; s < spec.n_seq; ++s) n_links += spec.links[spec.n_windows + s];
+    char line[256];
+    snprintf(line, sizeof(line), "The period spectra: %llu rows of %u bins, %llu links; links %.3f ms, histograms %.3f ms on the device.",
+             (unsigned long long)spec.n_rows, spec.max_period + 1, (unsigned long long)n_links, spec.links_ms, spec.hist_ms);
+    log_line(LOG_VERBOSE, line);
+    for (int which = 0; which < 2; ++which) {
+        const std::string& to = which == 0 ? file : hist_file;
+        if (to.empty()) continue;
+        char* text = nullptr;
+        uint64_t len = 0;
+        if ((which == 0 ? cl_periods_tsv : cl_periods_hist_tsv)(&spec, names.data(), fa.lengths, scope, &text, &len)) { err = "the period spectra: " + lib_error(); return false; }
+        FILE* f = fopen(to.c_str(), "wb");
+        const bool written = f && fwrite(text, 1, len, f) == len;
+        free(text);
+        if ((f && fclose(f) != 0) || !written) { err = "could not write the period spectra to " + to; return false; }
+    }
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -484,13 +522,25 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --dotplot-min-identity FLOAT  With --dotplot, keep a window pair from this identity in percent on [86]\n");
     fprintf(o, " --dotplot-pairs all|self    With --dotplot, compare all windows or only the windows of the same sequence [all]\n");
     fprintf(o, " --dotplot-only              With --dotplot, end after writing the map: nothing is aligned or printed\n");
+    fprintf(o, " --periods FILE              Write the repeat period spectra of the input sequences, one row per peak of every sequence and window, to FILE (which must not exist yet)\n");
+    fprintf(o, " --periods-hist FILE         With --periods, write the non-zero bins of every spectrum to FILE (which must not exist yet)\n");
+    fprintf(o, " --periods-k INT             With --periods, the k-mer length, 1 to 31 [8]\n");
+    fprintf(o, " --periods-window INT        With --periods, the window in bases, 1 to 1048576 [10000]\n");
+    fprintf(o, " --periods-max INT           With --periods, the longest period counted, 1 to 16383 [8000]\n");
+    fprintf(o, " --periods-peaks INT         With --periods, the peaks written per row, 1 to 16 [3]\n");
+    fprintf(o, " --periods-radius INT        With --periods, a peak is the largest count within INT bins on either side, 1 to 64 [1]\n");
+    fprintf(o, " --periods-min-period INT    With --periods, the shortest period that can be a peak [1]\n");
+    fprintf(o, " --periods-min-count INT     With --periods, the least count of a peak [2]\n");
+    fprintf(o, " --periods-scope WORD        With --periods, the rows written: both, sequences or windows [both]\n");
+    fprintf(o, " --periods-only              With --periods, end after writing the spectra: nothing is aligned or printed\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
     fprintf(o, "-t sets worker contexts; --devices, --infer-tree, --refine-tree, --tree-out, --pair-stats, --dist-out, --pair-profile, --window,\n");
     fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement, --graph, --msa-out, --column-stats, --variable-sites, --msa-layout,\n");
-    fprintf(o, "--site-min-minor, --site-max-gaps, --dotplot, --dotplot-k, --dotplot-window, --dotplot-min-identity, --dotplot-pairs and --dotplot-only\n");
-    fprintf(o, "are added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "--site-min-minor, --site-max-gaps, --dotplot, --dotplot-k, --dotplot-window, --dotplot-min-identity, --dotplot-pairs, --dotplot-only,\n");
+    fprintf(o, "--periods, --periods-hist, --periods-k, --periods-window, --periods-max, --periods-peaks, --periods-radius, --periods-min-period,\n");
+    fprintf(o, "--periods-min-count, --periods-scope and --periods-only are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -519,6 +569,10 @@ int run(int argc, char** argv) {
     std::string dotplot, dotplot_k_arg, dotplot_window_arg, dotplot_identity_arg, dotplot_pairs_arg;
     bool have_dotplot_k = false, have_dotplot_window = false, have_dotplot_identity = false, have_dotplot_pairs = false, dotplot_only = false;
     bool beside_dotplot_only = false;   // an option --dotplot-only does not go with
+    std::string periods, periods_hist, periods_scope_arg;
+    std::string periods_arg[7];   // --periods-k, -window, -max, -peaks, -radius, -min-period, -min-count as given
+    bool have_periods_arg[7] = {false, false, false, false, false, false, false}, have_periods_scope = false, periods_only = false;
+    bool beside_periods_only = false;   // an option --periods-only does not go with
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
@@ -526,7 +580,9 @@ int run(int argc, char** argv) {
            OPT_PAIR_PROFILE = 1010, OPT_WINDOW = 1011, OPT_PAIR_EVENTS = 1012, OPT_MIN_EVENT = 1013,
            OPT_COMPARE_TO = 1014, OPT_PAIR_AGREEMENT = 1015, OPT_GRAPH = 1016,
            OPT_MSA_OUT = 1017, OPT_COLUMN_STATS = 1018, OPT_VARIABLE_SITES = 1019, OPT_MSA_LAYOUT = 1020, OPT_SITE_MIN_MINOR = 1021, OPT_SITE_MAX_GAPS = 1022,
-           OPT_DOTPLOT = 1023, OPT_DOTPLOT_K = 1024, OPT_DOTPLOT_WINDOW = 1025, OPT_DOTPLOT_MIN_IDENTITY = 1026, OPT_DOTPLOT_PAIRS = 1027, OPT_DOTPLOT_ONLY = 1028 };
+           OPT_DOTPLOT = 1023, OPT_DOTPLOT_K = 1024, OPT_DOTPLOT_WINDOW = 1025, OPT_DOTPLOT_MIN_IDENTITY = 1026, OPT_DOTPLOT_PAIRS = 1027, OPT_DOTPLOT_ONLY = 1028,
+           OPT_PERIODS = 1029, OPT_PERIODS_HIST = 1030, OPT_PERIODS_K = 1031, OPT_PERIODS_WINDOW = 1032, OPT_PERIODS_MAX = 1033, OPT_PERIODS_PEAKS = 1034,
+           OPT_PERIODS_RADIUS = 1035, OPT_PERIODS_MIN_PERIOD = 1036, OPT_PERIODS_MIN_COUNT = 1037, OPT_PERIODS_SCOPE = 1038, OPT_PERIODS_ONLY = 1039 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -573,6 +629,17 @@ int run(int argc, char** argv) {
         {"dotplot-min-identity", required_argument, nullptr, OPT_DOTPLOT_MIN_IDENTITY},
         {"dotplot-pairs", required_argument, nullptr, OPT_DOTPLOT_PAIRS},
         {"dotplot-only", no_argument, nullptr, OPT_DOTPLOT_ONLY},
+        {"periods", required_argument, nullptr, OPT_PERIODS},
+        {"periods-hist", required_argument, nullptr, OPT_PERIODS_HIST},
+        {"periods-k", required_argument, nullptr, OPT_PERIODS_K},
+        {"periods-window", required_argument, nullptr, OPT_PERIODS_WINDOW},
+        {"periods-max", required_argument, nullptr, OPT_PERIODS_MAX},
+        {"periods-peaks", required_argument, nullptr, OPT_PERIODS_PEAKS},
+        {"periods-radius", required_argument, nullptr, OPT_PERIODS_RADIUS},
+        {"periods-min-period", required_argument, nullptr, OPT_PERIODS_MIN_PERIOD},
+        {"periods-min-count", required_argument, nullptr, OPT_PERIODS_MIN_COUNT},
+        {"periods-scope", required_argument, nullptr, OPT_PERIODS_SCOPE},
+        {"periods-only", no_argument, nullptr, OPT_PERIODS_ONLY},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -582,6 +649,7 @@ int run(int argc, char** argv) {
         const char* name = nullptr;   // the parameter this option sets from its argument
         const char* value = optarg;
         if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_DOTPLOT && o <= OPT_DOTPLOT_ONLY)) beside_dotplot_only = true;
+        if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_PERIODS && o <= OPT_PERIODS_ONLY)) beside_periods_only = true;
         switch (o) {
         case 'T': name = "tree_name"; break;
         case 'A': name = "all_pairs_prefix"; break;
@@ -630,6 +698,15 @@ int run(int argc, char** argv) {
         case OPT_DOTPLOT_MIN_IDENTITY: dotplot_identity_arg = optarg; have_dotplot_identity = true; break;
         case OPT_DOTPLOT_PAIRS: dotplot_pairs_arg = optarg; have_dotplot_pairs = true; break;
         case OPT_DOTPLOT_ONLY: dotplot_only = true; break;
+        case OPT_PERIODS: periods = optarg; break;
+        case OPT_PERIODS_HIST: periods_hist = optarg; break;
+        case OPT_PERIODS_K: case OPT_PERIODS_WINDOW: case OPT_PERIODS_MAX: case OPT_PERIODS_PEAKS: case OPT_PERIODS_RADIUS: case OPT_PERIODS_MIN_PERIOD:
+        case OPT_PERIODS_MIN_COUNT:
+            periods_arg[o - OPT_PERIODS_K] = optarg;
+            have_periods_arg[o - OPT_PERIODS_K] = true;
+            break;
+        case OPT_PERIODS_SCOPE: periods_scope_arg = optarg; have_periods_scope = true; break;
+        case OPT_PERIODS_ONLY: periods_only = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -673,6 +750,8 @@ int run(int argc, char** argv) {
 
     if (dotplot_only && !dotplot.empty() && beside_dotplot_only)
         return fail("--dotplot-only goes with the --dotplot options, -v and --devices alone: nothing else is run");
+    if (periods_only && !periods.empty() && beside_periods_only)
+        return fail("--periods-only goes with the --periods options, -v and --devices alone: nothing else is run");
     if (!config_name.empty()) {
         if (generate(cfg) != generate(own.defaults))
             fprintf(stderr, "warning: All other command-line arguments are being overridden by config file parameters.\n\n");
@@ -718,6 +797,46 @@ int run(int argc, char** argv) {
                                         config_value(cfg, "subalignments_filepath")};
         for (const std::string& other : others)
             if (dotplot == other) return fail("--dotplot names the file of another output option");
+    }
+    // --periods and its options, checked the same way
+    cl_periods_params periods_params;
+    cl_periods_params_default(&periods_params);
+    int periods_scope = 0;
+    {
+        struct { const char* opt; const char* what; uint64_t most; } const numbers[7] = {
+            {"--periods-k", "a k-mer length from 1 to 31", 31}, {"--periods-window", "a whole number of bases from 1 to 1048576", 1u << 20},
+            {"--periods-max", "a period from 1 to 16383", 16383}, {"--periods-peaks", "a number of peaks from 1 to 16", 16},
+            {"--periods-radius", "a number of bins from 1 to 64", 64}, {"--periods-min-period", "a period, at least 1", 0xFFFFFFFFull},
+            {"--periods-min-count", "a count, at least 1", 0xFFFFFFFFull}};
+        if (periods.empty()) {
+            const char* lone = !periods_hist.empty() ? "--periods-hist" : have_periods_scope ? "--periods-scope" : periods_only ? "--periods-only" : nullptr;
+            for (int i = 6; i >= 0; --i) if (have_periods_arg[i]) lone = numbers[i].opt;
+            if (lone) return fail(std::string(lone) + " needs --periods");
+        } else {
+            if (have_graph) return fail("--periods cannot be combined with --graph: it reads the sequences of a FASTA");
+            uint64_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < 7; ++i)
+                if (have_periods_arg[i] && (!parse_positive(periods_arg[i], v[i]) || v[i] > numbers[i].most))
+                    return fail(std::string(numbers[i].opt) + " expects " + numbers[i].what + ", got '" + periods_arg[i] + "'");
+            if (have_periods_arg[0]) periods_params.k = (int)v[0];
+            uint32_t* const into[7] = {nullptr, &periods_params.window, &periods_params.max_period, &periods_params.n_peaks, &periods_params.peak_radius,
+                                       &periods_params.min_period, &periods_params.min_count};
+            for (int i = 1; i < 7; ++i) if (have_periods_arg[i]) *into[i] = (uint32_t)v[i];
+            if (have_periods_scope) {
+                if (periods_scope_arg == "both") periods_scope = 0;
+                else if (periods_scope_arg == "sequences") periods_scope = 1;
+                else if (periods_scope_arg == "windows") periods_scope = 2;
+                else return fail("--periods-scope expects both, sequences or windows, got '" + periods_scope_arg + "'");
+            }
+            periods_params.want_hist = periods_hist.empty() ? 0 : 1;
+            if (std::ifstream(periods).good()) return fail("Period spectra file already exists: " + periods);
+            if (!periods_hist.empty() && std::ifstream(periods_hist).good()) return fail("Period histogram file already exists: " + periods_hist);
+            if (periods == periods_hist) return fail("--periods and --periods-hist name the same file");
+            const std::string others[11] = {tree_out, pair_stats, dist_out, pair_profile, pair_events, pair_agreement, msa_out, column_stats, variable_sites,
+                                            config_value(cfg, "subalignments_filepath"), dotplot};
+            for (const std::string& other : others)
+                if (periods == other || (!periods_hist.empty() && periods_hist == other)) return fail("--periods and --periods-hist cannot name the file of another output option");
+        }
     }
     // the tree options of this project, checked before anything is read or opened
     if (infer_tree && !config_value(cfg, "tree_name").empty()) return fail("--infer-tree cannot be combined with a guide tree (-T or tree_name)");
@@ -844,6 +963,15 @@ int run(int argc, char** argv) {
     for (uint64_t i = 0; i < fa.n_sequences; ++i) n_bases += fa.lengths[i];
     cl_fasta_free(&fa);
     if (!dotplot.empty() && n_bases >= (1ull << 30)) return fail("--dotplot takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
+    if (!periods.empty() && n_bases >= (1ull << 30)) return fail("--periods takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
+    if (periods_only) {   // no alignment, nothing on standard output
+        if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
+        own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
+        if (!own.ctx) return fail("no usable GPU: " + lib_error());
+        if (!write_periods(own.ctx, fasta_text, periods_params, periods_scope, periods, periods_hist, err)) return fail(err);
+        log_line(LOG_MINIMAL, "Wrote the period spectra to " + periods + ", exiting.");
+        return 0;
+    }
     if (dotplot_only) {   // no alignment, nothing on standard output
         if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
         own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
@@ -891,6 +1019,10 @@ int run(int argc, char** argv) {
     if (!dotplot.empty()) {
         log_line(LOG_BASIC, "Writing the dot plot.");
         if (!write_dotplot(own.ctx, fasta_text, dotplot_params, dotplot, err)) return fail(err);
+    }
+    if (!periods.empty()) {
+        log_line(LOG_BASIC, "Writing the period spectra.");
+        if (!write_periods(own.ctx, fasta_text, periods_params, periods_scope, periods, periods_hist, err)) return fail(err);
     }
     if (infer_tree) {   // the tree goes to cl_msa exactly as the text of a -T file would
         log_line(LOG_BASIC, "Inferring a guide tree from k-mer distances.");

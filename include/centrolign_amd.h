@@ -1085,6 +1085,68 @@ int  cl_kmer_dotplot_compute(cl_context* ctx, const char* const* sequences, cons
 int  cl_dotplot_tsv(const cl_dotplot* plot, const char* const* names, const uint64_t* lengths, char** text_out, uint64_t* len_out /* may be NULL */);
 void cl_dotplot_free(cl_dotplot* out);
 
+/* --- repeat period spectra (the CLI's --periods; the reference has none) ------------------------------------------------------------------------
+ * What the arrays are made of, as NTRprism and HORmon-style scripts ask it: the spacings between neighbouring occurrences of a k-mer, counted per
+ * window and per sequence, and the peaks of those counts (the monomer length, the higher-order-repeat period).  Every number is an integer and
+ * nothing depends on scheduling.
+ * Windows and k-mers are those of cl_kmer_dotplot_*: g = win_off[s] + p / W, G = win_off[n]; k characters of ACGTacgt, forward strand; a run
+ *   holding any other character is no k-mer.  (The window may be shorter than k here.)
+ * Links.  An occurrence is a position p of sequence s at which a k-mer starts; it belongs to the window of p.  Its successor p' is the next
+ *   occurrence of the same k-mer in the same sequence, d = p' - p.  Every occurrence adds exactly one count to its window's row: to bin d if it
+ *   has a successor and 1 <= d <= D = max_period (a "link"); to bin 0 ("far") if it has one and d > D; to `last` if it has none.  So for every
+ *   row kmers = links + far + last, with links = the sum of bins 1..D.
+ * Rows.  R = G + n.  Rows 0..G-1 are the windows; row G + s is the total of sequence s, the element-wise sum of its windows' rows, with peaks of
+ *   its own.  A row has D + 1 bins.
+ * Peaks of a row h (read h[0] and h[D + 1] as 0 here: bin 0, "far", is not a period).  d in min_period..D is a peak iff h[d] >= min_count,
+ *   h[d] > h[e] for every e in [d - r, d) with e >= 1, and h[d] >= h[e] for every e in (d, d + r] with e <= D, r = peak_radius: on a plateau the
+ *   leftmost bin wins.  The row's peaks are the n_peaks best by (count descending, period ascending); unused slots are {0, 0}.
+ * Limits.  k in 1..31; window in 1..2^20; max_period in 1..16383 (a row is at most 64 KiB); n_peaks in 1..16; peak_radius in 1..64;
+ *   min_period >= 1; min_count >= 1; n >= 1; the lengths add up to less than 2^30; R * (D + 1) <= 2^28.  Anything else is
+ *   CL_ERR_INVALID_ARGUMENT with a cl_last_error that names the argument.
+ * cl_period_spectrum_host: the definition, written plainly on the host (std::sort per sequence); no context, no GPU.
+ * cl_period_spectrum_compute: the device path (periods_kernels.hip) with the same bytes in every field but the two times.  want_hist = 0: hist
+ *   is NULL and the rows never leave the device.  links_ms / hist_ms: device time by events of the link phase (keys, two sorts, links) and of the
+ *   histogram phase (window rows, totals, peaks); 0 from the host call.
+ * cl_period_peaks_host: the peak rule alone on one row of max_period + 1 bins (uses n_peaks, peak_radius, min_period, min_count of params);
+ *   the host path uses this function for every row.
+ * cl_periods_tsv: host only.  A header line, then sample start end kmers links far rank period count share, tab-separated: one row per peak,
+ *   rank from 1, share = count / links as %.9g; a row without a peak is one line with 0 0 0 0 in the last four fields.  Per sequence first its
+ *   total (start 0, end L_s), then its windows ascending; scope 0: both, 1: sequences only, 2: windows only.  Coordinates 0-based and half-open,
+ *   the end clipped.  cl_periods_hist_tsv: sample start end period count for the non-zero bins 1..D of the same rows in the same order;
+ *   CL_ERR_INVALID_ARGUMENT if hist is NULL.  Every line ends with a line end; text returned through char** is malloc'ed.
+ * The arrays of a cl_period_spectrum are malloc'ed: release them with cl_period_spectrum_free. */
+typedef struct cl_periods_params {
+    int      k;             /* 8 */
+    uint32_t window;        /* 10000 */
+    uint32_t max_period;    /* 8000 */
+    uint32_t n_peaks;       /* 3 */
+    uint32_t peak_radius;   /* 1 */
+    uint32_t min_period;    /* 1 */
+    uint32_t min_count;     /* 2 */
+    int      want_hist;     /* 1 */
+} cl_periods_params;
+typedef struct cl_period_peak { uint32_t period, count; } cl_period_peak;
+typedef struct cl_period_spectrum {
+    uint64_t  n_seq, n_windows, n_rows;
+    int       k;
+    uint32_t  window, max_period, n_peaks;
+    uint64_t* win_off;                       /* [n_seq + 1] */
+    uint32_t *kmers, *links, *far, *last;    /* [n_rows] each */
+    cl_period_peak* peaks;                   /* [n_rows * n_peaks] */
+    uint32_t* hist;                          /* [n_rows * (max_period + 1)], bin-major within a row; NULL with want_hist = 0 */
+    float     links_ms, hist_ms;             /* device time by events */
+} cl_period_spectrum;
+void cl_periods_params_default(cl_periods_params* params);
+int  cl_period_spectrum_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_periods_params* params, cl_period_spectrum* out);
+int  cl_period_spectrum_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_periods_params* params,
+                                cl_period_spectrum* out);
+int  cl_period_peaks_host(const uint32_t* row /* [max_period + 1] */, uint32_t max_period, const cl_periods_params* params, cl_period_peak* out /* [n_peaks] */);
+int  cl_periods_tsv(const cl_period_spectrum* spec, const char* const* names, const uint64_t* lengths, int scope, char** text_out,
+                    uint64_t* len_out /* may be NULL */);
+int  cl_periods_hist_tsv(const cl_period_spectrum* spec, const char* const* names, const uint64_t* lengths, int scope, char** text_out,
+                         uint64_t* len_out /* may be NULL */);
+void cl_period_spectrum_free(cl_period_spectrum* out);
+
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
  * from.  Enums are integers.  Parameters are named as in the reference; a value is given and read back as config text (the same parsers
