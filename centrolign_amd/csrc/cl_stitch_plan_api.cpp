@@ -1684,7 +1684,8 @@ int upload_plan(cl_context* ctx, cl_stitch_plan* pl, const Packed& pk, LaunchLis
     pl->dev.out_len = pl->d_out_len.p;
     pl->dev.out_score = pl->d_out_score.p;
     pl->dev.out_status = pl->d_out_status.p;
-    { const char* e = getenv("CL_SPAN_DEBUG_FAIL"); pl->dev.debug_span_fail = e && e[0] == '1' ? 1 : 0; }   // test hook: every spanning chain pair reports status 9
+    { const char* e = getenv("CL_SPAN_DEBUG_FAIL"); pl->dev.debug_flags = e && e[0] == '1' ? 1 : 0; }   // test hook: every spanning chain pair reports status 9
+    { const char* e = getenv("CL_LANE_CELLS"); if (e && !strcmp(e, "general")) pl->dev.debug_flags |= 2; }   // A/B, tests (read per plan): popoa_lane_kernel's steps that are not the usual one all take the general cell
     { const char* e = getenv("CL_DEBUG_SKIP_TRACEBACK"); pl->dev.skip_traceback = e ? atoi(e) : 0; }   // measurement hook: 1 no traceback, 3 also no plane stores in the systolic kernel
     if (hipEventCreate(&pl->ev_start) != hipSuccess || hipEventCreate(&pl->ev_stop) != hipSuccess) {
         set_error(ctx, "hipEventCreate failed");

@@ -14,7 +14,10 @@
 //     slot numbers are compile-time constants (the step loop is unrolled by four), so that nothing is moved to age a value — a conveyor move writes straight into the
 //     ring slot of its step;
 //   * the usual step — every active lane on a chain row at a chain column: one predecessor one back on both sides, no source, no saved column — is decided per step by
-//     one ballot and takes a straight-line cell of ~25 instructions (popoa_linear_kernel's); any other step takes the general cell below (masks over the distances);
+//     one ballot and takes a straight-line cell of ~25 instructions (popoa_linear_kernel's); any other step takes the general cell below (masks over the distances)
+//     or, in the DR = 2 shape, the ROW-GENERAL cell: in a chunk whose columns are all plain chain columns the general cell's column terms are -inf for every
+//     active lane and are left out (scripts/dev/lane_cells.py counts the classes on a plan's pairs; CL_LANE_CELLS=general: the general cell as before).  A
+//     column-general cell for strips of chain rows was measured too and gained nothing (docs/design/stitch_kernels.md);
 //   * nothing in a chunk of 32 steps loads from global memory: the chunk's column records are fetched one chunk ahead, and a strip's last DR rows reach the next strip
 //     of the same round through a window of 128 columns in LDS (the next ROUND's first strip, and a WIDE pair's next group, read them from the area behind the planes);
 //     on gfx9 loads and stores share one counter, a load in the loop would wait for every plane store in front of it;
@@ -115,7 +118,7 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
     g_i32* const sx = (g_i32*)(brow + (size_t)(S > 0 ? S - 1 : 0) * DR * CW * nC);
     __shared__ uint32_t gave_up;
     if (WIDE) { if (tid == 0) gave_up = 0; __syncthreads(); }
-    auto cell_index = [&](uint32_t row, uint32_t col) { return swap ? G.idx(col, row) : G.idx(row, col); };
+    auto cell_index = [&](uint32_t row, uint32_t col) __attribute__((always_inline)) { return swap ? G.idx(col, row) : G.idx(row, col); };
 
     // ---- prologue: the boundary cells' planes (closed forms; the traceback reads them) ----
     if (!(B.skip_traceback & 2) && (!WIDE || grp == 0)) {
@@ -158,7 +161,9 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
     uint32_t pidx = 0;                         // its current cell in the planes
     int32_t ownBnd = CL_NEG_INF, predBnd[DR];
     bool rowslow = false, strip_dr1 = true;
-    auto reset_strip = [&]() {
+    bool strip_src = false;                            // a source row among the strip's rows (the row-general cell, below)
+    const bool tiers = !(B.debug_flags & 2);       // CL_LANE_CELLS=general: every step that is not the usual one takes the general cell
+    auto reset_strip = [&]() __attribute__((always_inline)) {
         crec = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -186,7 +191,7 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
             if (s < S && c < Cn && (!WIDE || wave < GS)) {
                 const bool real = (s * 64u + lane + 1u) <= nR;
                 const uint32_t t0 = c * C;
-                auto fetch_columns = [&](uint32_t first, int32_t& rec, int32_t& bm) {   // lanes 0 .. C - 1: the records of columns first + 1 ..
+                auto fetch_columns = [&](uint32_t first, int32_t& rec, int32_t& bm) __attribute__((always_inline)) {   // lanes 0 .. C - 1: the records of columns first + 1 ..
                     const uint32_t colb = first + lane + 1;
                     const bool v = lane < C && colb <= nC;
                     rec = v ? (int32_t)colrec[colb - 1] : 0;
@@ -210,6 +215,7 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
                     }
                     rowslow = real && (rrec & 0x1Fu) != 1u;                           // anything but "one predecessor, the row above"
                     strip_dr1 = __ballot(real && (rrec & 0xEu)) == 0ull;               // no row of the strip reaches further than one row up: the conveyor's first stage does
+                    strip_src = __ballot(real && (rrec & 0x10u)) != 0ull;
                     fetch_columns(0, nrec, nbm);
                 }
                 // this chunk's columns were fetched a chunk ago; the next chunk's are asked for now and not waited for before the chunk is over
@@ -267,8 +273,11 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
                 const bool rsrc = (rrec >> 4) & 1u;
 
                 // one step of the sweep; Q = step & 3 names the ring slots.  DRS = conveyor stages that are run (1 when no row of the strip needs more)
-                auto step = [&](auto qc, auto drs, uint32_t t) {
-                    constexpr int Q = decltype(qc)::value, P1 = (Q + 3) & 3, P2 = (Q + 2) & 3, P3 = (Q + 1) & 3, DRS = decltype(drs)::value;
+                // TIER = which cell a step that is not the usual one takes (fixed per unrolled body, see run_chunk below): 0 the general cell; 1 ROW-GENERAL over chain
+                // columns (every column of the chunk a plain chain column).  It drops from the general cell only terms that are -inf for every active lane, and
+                // keeps its clamps at -inf, so the planes are the same bytes
+                auto step = [&](auto qc, auto drs, auto tier, uint32_t t) __attribute__((always_inline)) {
+                    constexpr int Q = decltype(qc)::value, P1 = (Q + 3) & 3, P2 = (Q + 2) & 3, P3 = (Q + 1) & 3, DRS = decltype(drs)::value, TIER = decltype(tier)::value;
                     // the conveyor moves one lane: stage d takes the upper lane's stage d - 1 of the last step, stage 1 its last cell; lane 0 the rows above the strip
 #pragma unroll
                     for (int d = DRS - 1; d > 0; --d) {
@@ -308,6 +317,34 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
                             V[k] = imax(cMh[0][Q] - P.oe[k], cV[0][k] - P.ext[k]);
                             H[k] = imax(Mh[P1] - P.oe[k], Hh[k][P1] - P.ext[k]);
                             Mf = imax(Mf, imax(V[k], H[k]));
+                        }
+                    } else if (TIER == 1) {
+                        // row-general over chain columns: of the general cell below, what c1 alone leaves — V and the diagonal over the strip's row distances at
+                        // column distance 1, the boundary row only where the strip has a source row, the chain H
+                        if (active) {
+                            const int32_t sc = (labR == ((cr >> 8) & 0x7Fu)) ? P.match : -P.mismatch;
+                            int32_t Md = CL_NEG_INF;
+#pragma unroll
+                            for (int k = 0; k < NPW; ++k) V[k] = CL_NEG_INF;
+#pragma unroll
+                            for (int d = 0; d < DRS; ++d) {
+                                const bool on = (rmask >> d) & 1u;
+                                const int32_t mu = on ? cMh[d][Q] : CL_NEG_INF;
+#pragma unroll
+                                for (int k = 0; k < NPW; ++k) V[k] = imax(V[k], imax(mu - P.oe[k], (on ? cV[d][k] : CL_NEG_INF) - P.ext[k]));
+                                Md = imax(Md, on ? cMh[d][P1] : CL_NEG_INF);
+                            }
+                            if (strip_src) {
+                                const int32_t bnow = rsrc ? bMr[Q] : CL_NEG_INF;
+#pragma unroll
+                                for (int k = 0; k < NPW; ++k) V[k] = imax(V[k], bnow - P.oe[k]);
+                                Md = imax(Md, rsrc ? bMr[P1] : CL_NEG_INF);
+                            }
+#pragma unroll
+                            for (int k = 0; k < NPW; ++k) H[k] = imax(imax(Mh[P1], CL_NEG_INF) - P.oe[k], imax(Hh[k][P1], CL_NEG_INF) - P.ext[k]);
+                            Mf = Md + sc;
+#pragma unroll
+                            for (int k = 0; k < NPW; ++k) Mf = imax(Mf, imax(V[k], H[k]));
                         }
                     } else if (active) {
                         const uint32_t cmask = cr & 0x7u, nfar = (cr >> 5) & 3u;
@@ -427,15 +464,25 @@ __device__ __forceinline__ void lane_body(const ClDeviceBatch& B, const ClProbDe
                         }
                     }
                 };
-                auto run_chunk = [&](auto drs) {
+                auto run_chunk = [&](auto drs, auto tier) __attribute__((always_inline)) {
                     for (uint32_t jj = 0; jj < C; jj += 4) {
-                        step(LaneQ<0>{}, drs, t0 + jj);
-                        step(LaneQ<1>{}, drs, t0 + jj + 1);
-                        step(LaneQ<2>{}, drs, t0 + jj + 2);
-                        step(LaneQ<3>{}, drs, t0 + jj + 3);
+                        step(LaneQ<0>{}, drs, tier, t0 + jj);
+                        step(LaneQ<1>{}, drs, tier, t0 + jj + 1);
+                        step(LaneQ<2>{}, drs, tier, t0 + jj + 2);
+                        step(LaneQ<3>{}, drs, tier, t0 + jj + 3);
                     }
                 };
-                if (DR > 1 && !strip_dr1) run_chunk(LaneQ<DR>{}); else run_chunk(LaneQ<1>{});
+                // the tier is chosen per chunk, so that the unrolled bodies stay few (three: one stage, DR stages with the general cell, DR stages with the
+                // row-general cell): a strip whose rows reach further than one row up takes the row-general cell in the chunks whose columns — those in the lanes
+                // now (t0 - 63 .. t0) and the 32 fetched for this chunk — are all plain chain columns.  Only the DR = 2 shape has it: with it in the DR = 4 bodies
+                // too the kernels need more than the 168 VGPRs of three waves per SIMD, and scratch (docs/design/stitch_kernels.md)
+                auto not_plain = [](int32_t rec) { return rec != 0 && (rec & 0x7F) != 1; };
+                const bool chunk_plain = __ballot(not_plain(crec) || not_plain(frec)) == 0ull;
+                if (DR > 1 && !strip_dr1) {
+                    if constexpr (DR == 2) { if (tiers && chunk_plain) run_chunk(LaneQ<DR>{}, LaneQ<1>{}); else run_chunk(LaneQ<DR>{}, LaneQ<0>{}); }
+                    else run_chunk(LaneQ<DR>{}, LaneQ<0>{});
+                }
+                else run_chunk(LaneQ<1>{}, LaneQ<0>{});
                 }   // (not starved)
             }
         }

@@ -505,7 +505,7 @@ __device__ __forceinline__ void linear_span_body(const ClDeviceBatch& B, const C
         ok = v == 1;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (!ok || B.debug_span_fail) {
+    if (!ok || (B.debug_flags & 1)) {
         if (lane == 0) { B.out_len[prob] = 0; B.out_status[prob] = 9; }
         return;
     }
