@@ -1363,6 +1363,137 @@ def periods_hist_tsv(spectrum, names, lengths, scope="both"):
     return _periods_text("cl_periods_hist_tsv", spectrum, names, lengths, scope)
 
 
+class MonomersParams(C.Structure):
+    """cl_monomers_params"""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("insertion", C.c_int32), ("deletion", C.c_int32), ("chunk", C.c_uint32), ("overlap", C.c_uint32),
+                ("strands", C.c_int32)]
+
+
+class MonomerBlock(C.Structure):
+    """cl_monomer_block"""
+    _fields_ = [("sequence", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("monomer", C.c_uint32), ("score", C.c_int32), ("flags", C.c_uint32)]
+
+
+class MonomerDecompositionC(C.Structure):
+    """cl_monomer_decomposition"""
+    _fields_ = [("n_seq", C.c_uint64), ("n_blocks", C.c_uint64), ("n_problems", C.c_uint64), ("seq_off", C.POINTER(C.c_uint64)), ("blocks", C.POINTER(MonomerBlock)),
+                ("dp_ms", C.c_float), ("trace_ms", C.c_float)]
+
+
+MONOMER_BLOCK = np.dtype([("sequence", np.uint32), ("start", np.uint32), ("end", np.uint32), ("monomer", np.uint32), ("score", np.int32), ("flags", np.uint32)])
+MONOMER_PARTIAL_LEFT, MONOMER_PARTIAL_RIGHT = 1, 2
+_MONOMERS_FIELDS = ("match", "mismatch", "insertion", "deletion", "chunk", "overlap", "strands")
+
+
+def _monomers_params(lib, params):
+    lib.cl_monomers_params_default.argtypes = [C.POINTER(MonomersParams)]
+    lib.cl_monomers_params_default.restype = None
+    p = MonomersParams()
+    lib.cl_monomers_params_default(C.byref(p))
+    for name, v in params.items():
+        if name not in _MONOMERS_FIELDS:
+            raise TypeError("no monomer parameter named %r" % name)
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def monomers_params_default():
+    """cl_monomers_params_default as a dict"""
+    p = _monomers_params(load_library(), {})
+    return {name: int(getattr(p, name)) for name in _MONOMERS_FIELDS}
+
+
+def _strings(items):
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in items]
+    return raw, (C.c_char_p * max(len(raw), 1))(*raw), np.array([len(s) for s in raw], dtype=np.uint64)
+
+
+def _monomer_decompose(ctx, sequences, templates, params, lengths=None):
+    lib = load_library()
+    raw, bufs, lens = _strings(sequences)
+    traw, tbufs, tlens = _strings(templates)
+    if lengths is not None:   # (tests: lengths that the buffers do not have, which must be refused before a base is read)
+        lens = np.array([int(x) for x in lengths], dtype=np.uint64)
+    n = len(raw)
+    p = _monomers_params(lib, params)
+    lib.cl_monomer_decomposition_free.argtypes = [C.POINTER(MonomerDecompositionC)]
+    lib.cl_monomer_decomposition_free.restype = None
+    out = MonomerDecompositionC()
+    tail = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MonomersParams), C.POINTER(MonomerDecompositionC)]
+    if ctx is None:
+        h = None
+        lib.cl_monomer_decompose_host.argtypes = tail
+        rc = lib.cl_monomer_decompose_host(bufs, lens.ctypes.data, n, tbufs, tlens.ctypes.data, len(traw), C.byref(p), C.byref(out))
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_monomer_decompose_compute.argtypes = [C.c_void_p] + tail
+        rc = lib.cl_monomer_decompose_compute(h, bufs, lens.ctypes.data, n, tbufs, tlens.ctypes.data, len(traw), C.byref(p), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        B = int(out.n_blocks)
+        return {"n_seq": int(out.n_seq), "n_blocks": B, "n_problems": int(out.n_problems),
+                "seq_off": np.ctypeslib.as_array(out.seq_off, shape=(n + 1,)).copy(),
+                "blocks": np.frombuffer(C.string_at(out.blocks, 24 * B), dtype=MONOMER_BLOCK).copy(),
+                "dp_ms": float(out.dp_ms), "trace_ms": float(out.trace_ms)}
+    finally:
+        lib.cl_monomer_decomposition_free(C.byref(out))
+
+
+def monomer_decompose_host(sequences, templates, _lengths=None, **params):
+    """cl_monomer_decompose_host (host only, the definition): `sequences` (str or bytes) cut into blocks of the `templates`, as a dict of n_seq,
+    n_blocks, n_problems, seq_off [n + 1] uint64, blocks [n_blocks] of MONOMER_BLOCK (sequence, start, end, monomer, score, flags; monomer M + m is
+    the reverse complement of template m) and the two device times (0 here).  params: the fields of cl_monomers_params; one left out or None keeps
+    the value of cl_monomers_params_default (match 1, mismatch -1, insertion -1, deletion -1, chunk 4096, overlap 512, strands 1)"""
+    return _monomer_decompose(None, sequences, templates, params, _lengths)
+
+
+def monomer_decompose(ctx, sequences, templates, **params):
+    """cl_monomer_decompose_compute: the same on the device, byte for byte"""
+    if ctx is None:
+        raise ValueError("monomer_decompose needs a context (monomer_decompose_host is the host call)")
+    return _monomer_decompose(ctx, sequences, templates, params)
+
+
+def _monomers_text(fn_name, dec, names, template_names, template_lengths, params):
+    lib = load_library()
+    n = dec["n_seq"]
+    if len(names) != n or len(template_names) != len(template_lengths):
+        raise ValueError("%d names for %d sequences, %d names for %d templates" % (len(names), n, len(template_names), len(template_lengths)))
+    blocks = np.ascontiguousarray(dec["blocks"], dtype=MONOMER_BLOCK)
+    seq_off = np.ascontiguousarray(dec["seq_off"], dtype=np.uint64)
+    d = MonomerDecompositionC(n_seq=n, n_blocks=len(blocks), n_problems=dec["n_problems"])
+    d.seq_off = seq_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    d.blocks = blocks.ctypes.data_as(C.POINTER(MonomerBlock))
+    _, arr, _ = _strings(names)
+    _, tarr, _ = _strings(template_names)
+    tlens = np.array([int(x) for x in template_lengths], dtype=np.uint64)
+    p = _monomers_params(lib, params)
+    fn = getattr(lib, fn_name)
+    fn.argtypes = [C.POINTER(MonomerDecompositionC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MonomersParams), C.POINTER(C.c_void_p),
+                   C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = fn(C.byref(d), arr, tarr, tlens.ctypes.data, len(tlens), C.byref(p), C.byref(text), C.byref(ln))
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return C.string_at(text.value, ln.value)
+    finally:
+        _libc_free(text)
+
+
+def monomers_tsv(dec, names, template_names, template_lengths, **params):
+    """cl_monomers_tsv (host only): one row per block of a monomer_decompose dict as bytes; params as given to the decomposition (match and strands
+    are read)"""
+    return _monomers_text("cl_monomers_tsv", dec, names, template_names, template_lengths, params)
+
+
+def monomers_summary_tsv(dec, names, template_names, template_lengths, **params):
+    """cl_monomers_summary_tsv (host only): blocks, bases and score per sequence, template and strand"""
+    return _monomers_text("cl_monomers_summary_tsv", dec, names, template_names, template_lengths, params)
+
+
 def neighbor_joining_newick(distance, names):
     """cl_neighbor_joining_newick (host only): the midpoint-rooted neighbor-joining tree of an [n, n] distance matrix as Newick text"""
     lib = load_library()
@@ -1933,6 +2064,8 @@ EXPORTED_SYMBOLS = [
     "cl_dotplot_params_default", "cl_kmer_dotplot_host", "cl_kmer_dotplot_compute", "cl_dotplot_tsv", "cl_dotplot_free",
     "cl_periods_params_default", "cl_period_spectrum_host", "cl_period_spectrum_compute", "cl_period_peaks_host", "cl_periods_tsv", "cl_periods_hist_tsv",
     "cl_period_spectrum_free",
+    "cl_monomers_params_default", "cl_monomer_decompose_host", "cl_monomer_decompose_compute", "cl_monomers_tsv", "cl_monomers_summary_tsv",
+    "cl_monomer_decomposition_free",
 ]
 
 

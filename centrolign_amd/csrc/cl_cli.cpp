@@ -19,6 +19,8 @@
 //     --dotplot-min-identity, --dotplot-pairs) before the alignment starts; --dotplot-only ends the run there;
 //   - --periods FILE writes the repeat period spectra of the input sequences (cl_period_spectrum_compute; --periods-hist and the --periods-*
 //     options) before the alignment starts; --periods-only ends the run there;
+//   - --monomers FILE with --monomers-templates FASTA writes which monomer stands where on every input sequence (cl_monomer_decompose_compute;
+//     --monomers-summary and the --monomers-* options) before the alignment starts; --monomers-only ends the run there;
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -30,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -469,6 +472,77 @@ bool write_periods(cl_context* ctx, const std::string& fasta_text, const cl_peri
     return true;
 }
 
+// --monomers / --monomers-summary: the monomer decomposition of the FASTA's sequences, named as --pair-stats names them
+struct MonomerTemplates {
+    std::vector<std::string> names, bases;
+    std::vector<const char*> name_ptr, base_ptr;
+    std::vector<uint64_t> lengths;
+};
+
+// the templates of --monomers-templates, held to the library's limits (host only)
+bool read_monomer_templates(const std::string& file, int strands, MonomerTemplates& t, std::string& err) {
+    std::string text;
+    {
+        std::ifstream in(file, std::ios::binary);
+        if (!in) { err = "--monomers-templates: cannot open " + file; return false; }
+        text.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+    }
+    cl_fasta fa;
+    if (cl_parse_fasta(nullptr, text.data(), text.size(), &fa)) { err = "--monomers-templates " + file + ": " + lib_error(); return false; }
+    struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
+    if (fa.n_sequences < 1) { err = "--monomers-templates " + file + " holds no template"; return false; }
+    uint64_t total = 0;
+    for (uint64_t m = 0; m < fa.n_sequences; ++m) {
+        if (fa.lengths[m] < 1 || fa.lengths[m] > 1024) {
+            err = "--monomers-templates: template " + std::string(fa.names[m]) + " has " + std::to_string(fa.lengths[m]) + " bases, not 1 to 1024";
+            return false;
+        }
+        total += fa.lengths[m] * (uint64_t)strands;
+        t.names.push_back(fa.names[m]);
+        t.bases.push_back(std::string(fa.sequences[m], fa.lengths[m]));
+        t.lengths.push_back(fa.lengths[m]);
+    }
+    if (total > 8192) { err = "--monomers-templates: " + std::to_string(total) + " template bases in all (both strands counted), more than 8192"; return false; }
+    for (size_t m = 0; m < t.names.size(); ++m) { t.name_ptr.push_back(t.names[m].c_str()); t.base_ptr.push_back(t.bases[m].c_str()); }
+    return true;
+}
+
+bool write_monomers(cl_context* ctx, const std::string& fasta_text, const MonomerTemplates& t, const cl_monomers_params& params, const std::string& file,
+                    const std::string& summary_file, std::string& err) {
+    cl_fasta fa;
+    if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) { err = lib_error(); return false; }
+    struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
+    std::vector<std::string> shown(fa.names, fa.names + fa.n_sequences);
+    std::vector<const char*> names;
+    for (std::string& nm : shown) { std::replace(nm.begin(), nm.end(), '/', '_'); names.push_back(nm.c_str()); }
+    cl_monomer_decomposition dec;
+    if (cl_monomer_decompose_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, t.base_ptr.data(), t.lengths.data(), t.lengths.size(), &params, &dec)) {
+        const char* e = cl_last_error(ctx);
+        err = std::string("the monomer decomposition: ") + (e && *e ? e : "failed");
+        return false;
+    }
+    struct FreeDecomposition { cl_monomer_decomposition* d; ~FreeDecomposition() { cl_monomer_decomposition_free(d); } } free_decomposition{&dec};
+    char line[256];
+    snprintf(line, sizeof(line), "The monomer decomposition: %llu problems, %llu blocks; rows %.3f ms, blocks %.3f ms on the device.",
+             (unsigned long long)dec.n_problems, (unsigned long long)dec.n_blocks, dec.dp_ms, dec.trace_ms);
+    log_line(LOG_VERBOSE, line);
+    for (int which = 0; which < 2; ++which) {
+        const std::string& to = which == 0 ? file : summary_file;
+        if (to.empty()) continue;
+        char* text = nullptr;
+        uint64_t len = 0;
+        if ((which == 0 ? cl_monomers_tsv : cl_monomers_summary_tsv)(&dec, names.data(), t.name_ptr.data(), t.lengths.data(), t.lengths.size(), &params, &text, &len)) {
+            err = "the monomer decomposition: " + lib_error();
+            return false;
+        }
+        FILE* f = fopen(to.c_str(), "wb");
+        const bool written = f && fwrite(text, 1, len, f) == len;
+        free(text);
+        if ((f && fclose(f) != 0) || !written) { err = "could not write the monomer decomposition to " + to; return false; }
+    }
+    return true;
+}
+
 void print_help(const cl_config* defaults) {
     FILE* o = stderr;
     fprintf(o, "\n");
@@ -533,6 +607,17 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --periods-min-count INT     With --periods, the least count of a peak [2]\n");
     fprintf(o, " --periods-scope WORD        With --periods, the rows written: both, sequences or windows [both]\n");
     fprintf(o, " --periods-only              With --periods, end after writing the spectra: nothing is aligned or printed\n");
+    fprintf(o, " --monomers FILE             Write which monomer of --monomers-templates stands where on every input sequence, one row per block, to FILE (which must not exist yet)\n");
+    fprintf(o, " --monomers-templates FASTA  With --monomers (required), the monomer templates: 1 to 1024 bases each, at most 8192 in all (both strands counted)\n");
+    fprintf(o, " --monomers-summary FILE     With --monomers, write blocks, bases and score per sequence, template and strand to FILE (which must not exist yet)\n");
+    fprintf(o, " --monomers-strands WORD     With --monomers, the strands of the templates that are tried: forward or both [forward]\n");
+    fprintf(o, " --monomers-match INT        With --monomers, the score of a match, 1 to 64 [1]\n");
+    fprintf(o, " --monomers-mismatch INT     With --monomers, the score of a mismatch, -64 to -1 [-1]\n");
+    fprintf(o, " --monomers-insertion INT    With --monomers, the score of a sequence base next to no template base, -64 to -1 [-1]\n");
+    fprintf(o, " --monomers-deletion INT     With --monomers, the score of a template base next to no sequence base, -64 to -1 [-1]\n");
+    fprintf(o, " --monomers-chunk INT        With --monomers, the bases of a sequence that are decomposed at once, 64 to 1048576, or 0 for all of them [4096]\n");
+    fprintf(o, " --monomers-overlap INT      With --monomers, the bases a chunk reads beyond either end, 0 to 1048576; two template lengths or more [512]\n");
+    fprintf(o, " --monomers-only             With --monomers, end after writing the decomposition: nothing is aligned or printed\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
@@ -540,7 +625,9 @@ void print_help(const cl_config* defaults) {
     fprintf(o, "--pair-events, --min-event, --compare-to, --pair-agreement, --graph, --msa-out, --column-stats, --variable-sites, --msa-layout,\n");
     fprintf(o, "--site-min-minor, --site-max-gaps, --dotplot, --dotplot-k, --dotplot-window, --dotplot-min-identity, --dotplot-pairs, --dotplot-only,\n");
     fprintf(o, "--periods, --periods-hist, --periods-k, --periods-window, --periods-max, --periods-peaks, --periods-radius, --periods-min-period,\n");
-    fprintf(o, "--periods-min-count, --periods-scope and --periods-only are added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "--periods-min-count, --periods-scope, --periods-only, --monomers, --monomers-templates, --monomers-summary, --monomers-strands,\n");
+    fprintf(o, "--monomers-match, --monomers-mismatch, --monomers-insertion, --monomers-deletion, --monomers-chunk, --monomers-overlap and\n");
+    fprintf(o, "--monomers-only are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -573,6 +660,10 @@ int run(int argc, char** argv) {
     std::string periods_arg[7];   // --periods-k, -window, -max, -peaks, -radius, -min-period, -min-count as given
     bool have_periods_arg[7] = {false, false, false, false, false, false, false}, have_periods_scope = false, periods_only = false;
     bool beside_periods_only = false;   // an option --periods-only does not go with
+    std::string monomers, monomers_templates, monomers_summary, monomers_strands_arg;
+    std::string monomers_arg[6];   // --monomers-match, -mismatch, -insertion, -deletion, -chunk, -overlap as given
+    bool have_monomers_arg[6] = {false, false, false, false, false, false}, have_monomers_strands = false, monomers_only = false;
+    bool beside_monomers_only = false;   // an option --monomers-only does not go with
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
@@ -582,7 +673,10 @@ int run(int argc, char** argv) {
            OPT_MSA_OUT = 1017, OPT_COLUMN_STATS = 1018, OPT_VARIABLE_SITES = 1019, OPT_MSA_LAYOUT = 1020, OPT_SITE_MIN_MINOR = 1021, OPT_SITE_MAX_GAPS = 1022,
            OPT_DOTPLOT = 1023, OPT_DOTPLOT_K = 1024, OPT_DOTPLOT_WINDOW = 1025, OPT_DOTPLOT_MIN_IDENTITY = 1026, OPT_DOTPLOT_PAIRS = 1027, OPT_DOTPLOT_ONLY = 1028,
            OPT_PERIODS = 1029, OPT_PERIODS_HIST = 1030, OPT_PERIODS_K = 1031, OPT_PERIODS_WINDOW = 1032, OPT_PERIODS_MAX = 1033, OPT_PERIODS_PEAKS = 1034,
-           OPT_PERIODS_RADIUS = 1035, OPT_PERIODS_MIN_PERIOD = 1036, OPT_PERIODS_MIN_COUNT = 1037, OPT_PERIODS_SCOPE = 1038, OPT_PERIODS_ONLY = 1039 };
+           OPT_PERIODS_RADIUS = 1035, OPT_PERIODS_MIN_PERIOD = 1036, OPT_PERIODS_MIN_COUNT = 1037, OPT_PERIODS_SCOPE = 1038, OPT_PERIODS_ONLY = 1039,
+           OPT_MONOMERS = 1040, OPT_MONOMERS_TEMPLATES = 1041, OPT_MONOMERS_SUMMARY = 1042, OPT_MONOMERS_STRANDS = 1043, OPT_MONOMERS_MATCH = 1044,
+           OPT_MONOMERS_MISMATCH = 1045, OPT_MONOMERS_INSERTION = 1046, OPT_MONOMERS_DELETION = 1047, OPT_MONOMERS_CHUNK = 1048, OPT_MONOMERS_OVERLAP = 1049,
+           OPT_MONOMERS_ONLY = 1050 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -640,6 +734,17 @@ int run(int argc, char** argv) {
         {"periods-min-count", required_argument, nullptr, OPT_PERIODS_MIN_COUNT},
         {"periods-scope", required_argument, nullptr, OPT_PERIODS_SCOPE},
         {"periods-only", no_argument, nullptr, OPT_PERIODS_ONLY},
+        {"monomers", required_argument, nullptr, OPT_MONOMERS},
+        {"monomers-templates", required_argument, nullptr, OPT_MONOMERS_TEMPLATES},
+        {"monomers-summary", required_argument, nullptr, OPT_MONOMERS_SUMMARY},
+        {"monomers-strands", required_argument, nullptr, OPT_MONOMERS_STRANDS},
+        {"monomers-match", required_argument, nullptr, OPT_MONOMERS_MATCH},
+        {"monomers-mismatch", required_argument, nullptr, OPT_MONOMERS_MISMATCH},
+        {"monomers-insertion", required_argument, nullptr, OPT_MONOMERS_INSERTION},
+        {"monomers-deletion", required_argument, nullptr, OPT_MONOMERS_DELETION},
+        {"monomers-chunk", required_argument, nullptr, OPT_MONOMERS_CHUNK},
+        {"monomers-overlap", required_argument, nullptr, OPT_MONOMERS_OVERLAP},
+        {"monomers-only", no_argument, nullptr, OPT_MONOMERS_ONLY},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -650,6 +755,7 @@ int run(int argc, char** argv) {
         const char* value = optarg;
         if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_DOTPLOT && o <= OPT_DOTPLOT_ONLY)) beside_dotplot_only = true;
         if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_PERIODS && o <= OPT_PERIODS_ONLY)) beside_periods_only = true;
+        if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_MONOMERS && o <= OPT_MONOMERS_ONLY)) beside_monomers_only = true;
         switch (o) {
         case 'T': name = "tree_name"; break;
         case 'A': name = "all_pairs_prefix"; break;
@@ -707,6 +813,16 @@ int run(int argc, char** argv) {
             break;
         case OPT_PERIODS_SCOPE: periods_scope_arg = optarg; have_periods_scope = true; break;
         case OPT_PERIODS_ONLY: periods_only = true; break;
+        case OPT_MONOMERS: monomers = optarg; break;
+        case OPT_MONOMERS_TEMPLATES: monomers_templates = optarg; break;
+        case OPT_MONOMERS_SUMMARY: monomers_summary = optarg; break;
+        case OPT_MONOMERS_STRANDS: monomers_strands_arg = optarg; have_monomers_strands = true; break;
+        case OPT_MONOMERS_MATCH: case OPT_MONOMERS_MISMATCH: case OPT_MONOMERS_INSERTION: case OPT_MONOMERS_DELETION: case OPT_MONOMERS_CHUNK:
+        case OPT_MONOMERS_OVERLAP:
+            monomers_arg[o - OPT_MONOMERS_MATCH] = optarg;
+            have_monomers_arg[o - OPT_MONOMERS_MATCH] = true;
+            break;
+        case OPT_MONOMERS_ONLY: monomers_only = true; break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -752,6 +868,8 @@ int run(int argc, char** argv) {
         return fail("--dotplot-only goes with the --dotplot options, -v and --devices alone: nothing else is run");
     if (periods_only && !periods.empty() && beside_periods_only)
         return fail("--periods-only goes with the --periods options, -v and --devices alone: nothing else is run");
+    if (monomers_only && !monomers.empty() && beside_monomers_only)
+        return fail("--monomers-only goes with the --monomers options, -v and --devices alone: nothing else is run");
     if (!config_name.empty()) {
         if (generate(cfg) != generate(own.defaults))
             fprintf(stderr, "warning: All other command-line arguments are being overridden by config file parameters.\n\n");
@@ -836,6 +954,56 @@ int run(int argc, char** argv) {
                                             config_value(cfg, "subalignments_filepath"), dotplot};
             for (const std::string& other : others)
                 if (periods == other || (!periods_hist.empty() && periods_hist == other)) return fail("--periods and --periods-hist cannot name the file of another output option");
+        }
+    }
+    // --monomers and its options, checked the same way; the templates are read here: what is wrong with them needs no other input
+    cl_monomers_params monomers_params;
+    cl_monomers_params_default(&monomers_params);
+    MonomerTemplates monomer_templates;
+    {
+        static const char* const opts[6] = {"--monomers-match", "--monomers-mismatch", "--monomers-insertion", "--monomers-deletion", "--monomers-chunk", "--monomers-overlap"};
+        if (monomers.empty()) {
+            const char* lone = !monomers_templates.empty() ? "--monomers-templates" : !monomers_summary.empty() ? "--monomers-summary"
+                               : have_monomers_strands ? "--monomers-strands" : monomers_only ? "--monomers-only" : nullptr;
+            for (int i = 5; i >= 0; --i) if (have_monomers_arg[i]) lone = opts[i];
+            if (lone) return fail(std::string(lone) + " needs --monomers");
+        } else {
+            if (have_graph) return fail("--monomers cannot be combined with --graph: it reads the sequences of a FASTA");
+            if (monomers_templates.empty()) return fail("--monomers needs --monomers-templates");
+            uint64_t v = 0;
+            if (have_monomers_arg[0] && (!parse_positive(monomers_arg[0], v) || v > 64)) return fail("--monomers-match expects a score from 1 to 64, got '" + monomers_arg[0] + "'");
+            if (have_monomers_arg[0]) monomers_params.match = (int32_t)v;
+            int32_t* const penalty[3] = {&monomers_params.mismatch, &monomers_params.insertion, &monomers_params.deletion};
+            for (int i = 1; i <= 3; ++i) {
+                if (!have_monomers_arg[i]) continue;
+                char* end = nullptr;
+                errno = 0;
+                const long x = strtol(monomers_arg[i].c_str(), &end, 10);
+                if (monomers_arg[i].empty() || *end || errno || x < -64 || x > -1) return fail(std::string(opts[i]) + " expects a score from -64 to -1, got '" + monomers_arg[i] + "'");
+                *penalty[i - 1] = (int32_t)x;
+            }
+            if (have_monomers_arg[4] && (!parse_count(monomers_arg[4], v) || (v != 0 && v < 64) || v > (1u << 20)))
+                return fail("--monomers-chunk expects 0 or a whole number of bases from 64 to 1048576, got '" + monomers_arg[4] + "'");
+            if (have_monomers_arg[4]) monomers_params.chunk = (uint32_t)v;
+            if (have_monomers_arg[5] && (!parse_count(monomers_arg[5], v) || v > (1u << 20)))
+                return fail("--monomers-overlap expects a whole number of bases from 0 to 1048576, got '" + monomers_arg[5] + "'");
+            if (have_monomers_arg[5]) monomers_params.overlap = (uint32_t)v;
+            if (have_monomers_strands) {
+                if (monomers_strands_arg == "forward") monomers_params.strands = 1;
+                else if (monomers_strands_arg == "both") monomers_params.strands = 2;
+                else return fail("--monomers-strands expects forward or both, got '" + monomers_strands_arg + "'");
+            }
+            if (std::ifstream(monomers).good()) return fail("Monomer decomposition file already exists: " + monomers);
+            if (!monomers_summary.empty() && std::ifstream(monomers_summary).good()) return fail("Monomer summary file already exists: " + monomers_summary);
+            if (monomers == monomers_summary) return fail("--monomers and --monomers-summary name the same file");
+            const std::string others[13] = {tree_out, pair_stats, dist_out, pair_profile, pair_events, pair_agreement, msa_out, column_stats, variable_sites,
+                                            config_value(cfg, "subalignments_filepath"), dotplot, periods, periods_hist};
+            for (const std::string& other : others)
+                if (!other.empty() && (monomers == other || monomers_summary == other))
+                    return fail("--monomers and --monomers-summary cannot name the file of another output option");
+            if (monomers == monomers_templates || monomers_summary == monomers_templates) return fail("--monomers and --monomers-summary cannot name the templates' file");
+            std::string err;
+            if (!read_monomer_templates(monomers_templates, monomers_params.strands, monomer_templates, err)) return fail(err);
         }
     }
     // the tree options of this project, checked before anything is read or opened
@@ -964,6 +1132,15 @@ int run(int argc, char** argv) {
     cl_fasta_free(&fa);
     if (!dotplot.empty() && n_bases >= (1ull << 30)) return fail("--dotplot takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
     if (!periods.empty() && n_bases >= (1ull << 30)) return fail("--periods takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
+    if (!monomers.empty() && n_bases >= (1ull << 30)) return fail("--monomers takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
+    if (monomers_only) {   // no alignment, nothing on standard output
+        if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
+        own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
+        if (!own.ctx) return fail("no usable GPU: " + lib_error());
+        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomers, monomers_summary, err)) return fail(err);
+        log_line(LOG_MINIMAL, "Wrote the monomer decomposition to " + monomers + ", exiting.");
+        return 0;
+    }
     if (periods_only) {   // no alignment, nothing on standard output
         if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
         own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
@@ -1023,6 +1200,10 @@ int run(int argc, char** argv) {
     if (!periods.empty()) {
         log_line(LOG_BASIC, "Writing the period spectra.");
         if (!write_periods(own.ctx, fasta_text, periods_params, periods_scope, periods, periods_hist, err)) return fail(err);
+    }
+    if (!monomers.empty()) {
+        log_line(LOG_BASIC, "Writing the monomer decomposition.");
+        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomers, monomers_summary, err)) return fail(err);
     }
     if (infer_tree) {   // the tree goes to cl_msa exactly as the text of a -T file would
         log_line(LOG_BASIC, "Inferring a guide tree from k-mer distances.");

@@ -419,6 +419,15 @@ hipError_t cl_launch_subaln_write(const ClSubalnSide& s1, const ClSubalnSide& s2
                                   char* text, hipStream_t stream);
 uint64_t cl_subaln_pairs_per_block();
 
+// monomers_kernels.hip: the blocks of validated input (cl_monomers_api.cpp).  One problem: n rows of sequence `seq` that start at byte text_off of
+// the sequences laid back to back, row 0 being the sequence's position row0; the blocks whose (absolute) start lies in [keep_lo, keep_hi) are
+// kept; rec_off is the problem's first row in the record array.  codes / tmpl_off: the templates' base codes (0..3, 5: no base) back to back
+// and where each begins, reverse complements included.
+struct ClMonomerProblem { uint64_t text_off, rec_off; uint32_t n, row0, keep_lo, keep_hi, seq, pad; };
+int cl_monomers_device(cl_context* ctx, const char* const* seqs, const uint64_t* lens, uint64_t n, const std::vector<uint8_t>& codes,
+                       const std::vector<uint32_t>& tmpl_off, const cl_monomers_params* p, const std::vector<ClMonomerProblem>& problems,
+                       std::vector<cl_monomer_block>& blocks, float* dp_ms, float* trace_ms);
+
 // host-side parallel loop over [0, n): f(begin, end) on up to 32 threads (the reference is single-threaded; the host glue around the device
 // passes is not part of the compared arithmetic, every iteration writes its own outputs).  The threads come from ONE pool per process
 // (cl_api.cpp), made on first use: creating and destroying threads per loop costs an mmap / munmap of every stack, and those take the

@@ -76,6 +76,14 @@ def hor_sequences(seed, total_len, n_seq, mono_len=171, hor_n=12, mono_div=0.25,
     return (seqs, srcs) if track else seqs
 
 
+def hor_monomers(seed, mono_len=171, hor_n=12, mono_div=0.25):
+    """the hor_n monomers hor_sequences(seed, ...) builds its HOR from (the first draws of the same random stream): templates for the monomer
+    decomposition of those arrays"""
+    rng = random.Random(seed)
+    base = [rng.choice(_B) for _ in range(mono_len)]
+    return ["".join(_mut_track(rng, base, mono_div)[0]) for _ in range(hor_n)]
+
+
 def tandem_dup_sequences(seed, total_len, n_seq, dup_len, dup_at=None, dup_div=0.003, carriers=None, **kw):
     """hor_sequences in which some sequences carry a recent tandem duplication: a copy of [dup_at, dup_at + dup_len), mutated at rate
     dup_div, inserted right behind the original (inputs for the cyclisation path, the CLI's -c)"""

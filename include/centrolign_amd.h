@@ -1147,6 +1147,78 @@ int  cl_periods_hist_tsv(const cl_period_spectrum* spec, const char* const* name
                          uint64_t* len_out /* may be NULL */);
 void cl_period_spectrum_free(cl_period_spectrum* out);
 
+/* --- monomer decomposition (the CLI's --monomers; the reference has none) ----------------------------------------------------------------------
+ * Which monomer stands where: every sequence is cut into blocks, each block one (possibly partial) copy of one of the templates, so that the sum of
+ * the blocks' alignment scores is largest.  This is what StringDecomposer computes on the CPU.  Every number is an integer and nothing depends
+ * on scheduling.
+ * Templates and scores.  Templates B_0 .. B_{M-1}; with strands = 2 template M + m is the reverse complement of template m.  Bases are compared
+ *   after case folding; two bases match only if both are one of ACGT and equal, any other character matches nothing and is its own complement.
+ *   match >= 1; mismatch, insertion (a sequence base aligned to no template base) and deletion (a template base aligned to no sequence base)
+ *   <= -1.
+ * One problem is a range of n rows S[0 .. n) of one sequence.  A value is a pair (score, start), ordered by larger score, then larger start;
+ *   start lies in {-1, 0 .. n}, -1 meaning "began inside a template at the problem's left end"; adding a score changes the score only.
+ *   Row 0: H[0][m][0] = (0, 0), H[0][m][j] = (0, -1) for 1 <= j <= len_m, E[0] = 0.  Row i >= 1, 1 <= j <= len_m:
+ *     T[i][m][j] = max(H[i-1][m][j-1] + s(S[i-1], B_m[j-1]), H[i-1][m][j] + insertion)
+ *     D[i][m][j] = max over 1 <= k <= j of T[i][m][k] + (j - k) * deletion
+ *     rec[i]     = the maximum over m of D[i][m][len_m], ties to the smallest m, kept as (score, start, m); E[i] is its score
+ *     H[i][m][0] = (E[i], i);  H[i][m][j] = max(D[i][m][j], (E[i] + j * deletion, i))
+ *   Closing cell: the maximum of H[n][m][j] over all m and 1 <= j <= len_m, ties to the smallest m, then the largest j; n = 0: no block.
+ *   Blocks, read from the end: the closing cell gives the last block (max(start, 0), n, m), partial-right if j < len_m, partial-left if
+ *   start = -1; then i = that block's start, and while i > 0 rec[i] gives the block (max(start, 0), i, m), partial-left if start = -1, and i
+ *   becomes its start.  A block's score is the value it was read from minus E[its start] (saturated to 32 bits).
+ * Chunks.  chunk = C > 0 and overlap = V: a sequence of length L has ceil(L / C) problems; problem c covers rows [max(0, cC - V),
+ *   min(L, (c + 1)C + V)), and those of its blocks whose start lies in [cC, (c + 1)C) are kept, in absolute coordinates.  chunk = 0: every
+ *   sequence is one problem.  Blocks are ordered by sequence, then chunk, then start.  Seams are NOT repaired: the blocks of neighbouring chunks
+ *   may overlap or leave a gap at a seam; with an overlap of two template lengths or more this is rare.
+ * Limits.  1 <= M; every template 1..1024 bases; at most 8192 template bases in all after doubling; match in 1..64; mismatch, insertion and
+ *   deletion in -64..-1; chunk 0 or 64..2^20; overlap <= 2^20; strands 1 or 2; the lengths add up to less than 2^30 (checked before a base is
+ *   read).  Anything else is CL_ERR_INVALID_ARGUMENT with a cl_last_error that names the argument.
+ * cl_monomer_decompose_host: the definition, written plainly on the host; no context, no GPU.
+ * cl_monomer_decompose_compute: the device path (monomers_kernels.hip) with the same bytes in every field but the two times.  dp_ms / trace_ms:
+ *   device time by events of the DP kernel and of the trace (count, place, write); 0 from the host call.
+ * cl_monomers_tsv: host only.  A header line, then sample start end monomer strand score share partial, tab-separated, one row per block;
+ *   monomer is the forward template's name and strand + or -; share = score / (match * len_m) as %.9g; partial is one of . L R LR;
+ *   coordinates 0-based and half-open.  cl_monomers_summary_tsv: sample monomer strand blocks bases score per sequence, template and strand,
+ *   in that order, rows without a block omitted.  template_lengths are those of the n_templates forward templates.  Every line ends with a line
+ *   end; text returned through char** is malloc'ed.
+ * The arrays of a cl_monomer_decomposition are malloc'ed: release them with cl_monomer_decomposition_free. */
+typedef struct cl_monomers_params {
+    int32_t  match;       /* 1 */
+    int32_t  mismatch;    /* -1 */
+    int32_t  insertion;   /* -1 */
+    int32_t  deletion;    /* -1 */
+    uint32_t chunk;       /* 4096; 0: one problem per sequence */
+    uint32_t overlap;     /* 512 */
+    int32_t  strands;     /* 1: the templates as given, 2: and their reverse complements */
+} cl_monomers_params;
+#define CL_MONOMER_PARTIAL_LEFT  1u
+#define CL_MONOMER_PARTIAL_RIGHT 2u
+typedef struct cl_monomer_block {   /* 24 bytes */
+    uint32_t sequence, start, end;
+    uint32_t monomer;               /* template index; M + m: the reverse complement of template m */
+    int32_t  score;
+    uint32_t flags;                 /* bit 0: partial-left, bit 1: partial-right */
+} cl_monomer_block;
+typedef struct cl_monomer_decomposition {
+    uint64_t  n_seq, n_blocks, n_problems;
+    uint64_t* seq_off;              /* [n_seq + 1]: the blocks of sequence s are blocks[seq_off[s] .. seq_off[s + 1]) */
+    cl_monomer_block* blocks;       /* [n_blocks] */
+    float     dp_ms, trace_ms;      /* device time by events */
+} cl_monomer_decomposition;
+void cl_monomers_params_default(cl_monomers_params* params);
+int  cl_monomer_decompose_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const char* const* templates,
+                               const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params, cl_monomer_decomposition* out);
+int  cl_monomer_decompose_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, const char* const* templates,
+                                  const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params,
+                                  cl_monomer_decomposition* out);
+int  cl_monomers_tsv(const cl_monomer_decomposition* dec, const char* const* names, const char* const* template_names,
+                     const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params, char** text_out,
+                     uint64_t* len_out /* may be NULL */);
+int  cl_monomers_summary_tsv(const cl_monomer_decomposition* dec, const char* const* names, const char* const* template_names,
+                             const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params, char** text_out,
+                             uint64_t* len_out /* may be NULL */);
+void cl_monomer_decomposition_free(cl_monomer_decomposition* out);
+
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
  * from.  Enums are integers.  Parameters are named as in the reference; a value is given and read back as config text (the same parsers
