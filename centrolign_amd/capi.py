@@ -1494,6 +1494,229 @@ def monomers_summary_tsv(dec, names, template_names, template_lengths, **params)
     return _monomers_text("cl_monomers_summary_tsv", dec, names, template_names, template_lengths, params)
 
 
+class MonomerPileupC(C.Structure):
+    """cl_monomer_pileup"""
+    _fields_ = [("n_templates", C.c_uint64), ("col_off", C.POINTER(C.c_uint64)), ("columns", C.POINTER(C.c_uint32)), ("slots", C.POINTER(C.c_uint32)),
+                ("used", C.POINTER(C.c_uint64)), ("partial", C.POINTER(C.c_uint64)), ("long_", C.POINTER(C.c_uint64)), ("weak", C.POINTER(C.c_uint64)),
+                ("score_sum", C.POINTER(C.c_int64)), ("align_ms", C.c_float), ("count_ms", C.c_float)]
+
+
+class MonomerRound(C.Structure):
+    """cl_monomer_round"""
+    _fields_ = [("blocks", C.c_uint64), ("used", C.c_uint64), ("changed", C.c_uint64), ("dp_ms", C.c_float), ("trace_ms", C.c_float), ("align_ms", C.c_float),
+                ("count_ms", C.c_float)]
+
+
+class MonomerTemplatesC(C.Structure):
+    """cl_monomer_templates"""
+    _fields_ = [("n_templates", C.c_uint64), ("templates", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_uint64)), ("changed", C.POINTER(C.c_uint8)),
+                ("names", C.POINTER(C.c_char_p)), ("rounds", C.c_uint32), ("converged", C.c_int32), ("round", C.POINTER(MonomerRound))]
+
+
+def _dec_struct(dec):
+    """a monomer_decompose dict as a cl_monomer_decomposition over numpy arrays (returned with it: they must outlive the call)"""
+    blocks = np.ascontiguousarray(dec["blocks"], dtype=MONOMER_BLOCK)
+    seq_off = np.ascontiguousarray(dec["seq_off"], dtype=np.uint64)
+    d = MonomerDecompositionC(n_seq=dec["n_seq"], n_blocks=len(blocks), n_problems=dec["n_problems"])
+    d.seq_off = seq_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    d.blocks = blocks.ctypes.data_as(C.POINTER(MonomerBlock))
+    return d, (blocks, seq_off)
+
+
+def _pileup_dict(out):
+    M = int(out.n_templates)
+    col_off = np.ctypeslib.as_array(out.col_off, shape=(M + 1,)).copy()
+    total = int(col_off[M])
+    d = {"n_templates": M, "col_off": col_off,
+         "columns": np.ctypeslib.as_array(out.columns, shape=(total, 6)).copy(),
+         "slots": np.ctypeslib.as_array(out.slots, shape=(total + M, 5)).copy(),
+         "score_sum": np.ctypeslib.as_array(out.score_sum, shape=(M,)).copy(), "align_ms": float(out.align_ms), "count_ms": float(out.count_ms)}
+    for name in ("used", "partial", "long_", "weak"):
+        d[name] = np.ctypeslib.as_array(getattr(out, name), shape=(M,)).copy()
+    return d
+
+
+def _monomer_pileup(ctx, sequences, templates, dec, least_share, params, lengths=None):
+    lib = load_library()
+    raw, bufs, lens = _strings(sequences)
+    traw, tbufs, tlens = _strings(templates)
+    if lengths is not None:
+        lens = np.array([int(x) for x in lengths], dtype=np.uint64)
+    p = _monomers_params(lib, params)
+    d, keep = _dec_struct(dec)
+    lib.cl_monomer_pileup_free.argtypes = [C.POINTER(MonomerPileupC)]
+    lib.cl_monomer_pileup_free.restype = None
+    out = MonomerPileupC()
+    tail = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MonomersParams), C.POINTER(MonomerDecompositionC), C.c_uint32,
+            C.POINTER(MonomerPileupC)]
+    args = (bufs, lens.ctypes.data, len(raw), tbufs, tlens.ctypes.data, len(traw), C.byref(p), C.byref(d), int(least_share), C.byref(out))
+    if ctx is None:
+        h = None
+        lib.cl_monomer_pileup_host.argtypes = tail
+        rc = lib.cl_monomer_pileup_host(*args)
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_monomer_pileup_compute.argtypes = [C.c_void_p] + tail
+        rc = lib.cl_monomer_pileup_compute(h, *args)
+    del keep
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        return _pileup_dict(out)
+    finally:
+        lib.cl_monomer_pileup_free(C.byref(out))
+
+
+def monomer_pileup_host(sequences, templates, dec, least_share=0, _lengths=None, **params):
+    """cl_monomer_pileup_host (host only, the definition): the blocks of the monomer_decompose dict `dec` that are whole copies, aligned to their
+    templates and counted per column: a dict of n_templates, col_off [M + 1], columns [total, 6] (A, C, G, T, other, deleted), slots
+    [total + M, 5] (the first inserted base in front of a column; slot j of template m is row col_off[m] + m + j), used / partial / long_ / weak
+    [M], score_sum [M] and the two device times (0 here).  least_share: per mille of match * len a block's score must reach.  params: as given
+    to the decomposition"""
+    return _monomer_pileup(None, sequences, templates, dec, least_share, params, _lengths)
+
+
+def monomer_pileup(ctx, sequences, templates, dec, least_share=0, **params):
+    """cl_monomer_pileup_compute: the same on the device, byte for byte"""
+    if ctx is None:
+        raise ValueError("monomer_pileup needs a context (monomer_pileup_host is the host call)")
+    return _monomer_pileup(ctx, sequences, templates, dec, least_share, params)
+
+
+def _templates_dict(lib, out):
+    try:
+        M = int(out.n_templates)
+        return {"templates": [C.string_at(out.templates[m], int(out.lengths[m])).decode("latin-1") for m in range(M)],
+                "changed": [bool(out.changed[m]) for m in range(M)],
+                "names": [out.names[m].decode() for m in range(M)] if out.names else None,
+                "rounds": int(out.rounds), "converged": bool(out.converged),
+                "round": [{"blocks": int(r.blocks), "used": int(r.used), "changed": int(r.changed), "dp_ms": float(r.dp_ms), "trace_ms": float(r.trace_ms),
+                           "align_ms": float(r.align_ms), "count_ms": float(r.count_ms)} for r in (out.round[k] for k in range(int(out.rounds)))]}
+    finally:
+        lib.cl_monomer_templates_free(C.byref(out))
+
+
+def _pileup_struct(pileup):
+    M = int(pileup["n_templates"])
+    arrays = {"col_off": np.ascontiguousarray(pileup["col_off"], dtype=np.uint64), "columns": np.ascontiguousarray(pileup["columns"], dtype=np.uint32),
+              "slots": np.ascontiguousarray(pileup["slots"], dtype=np.uint32), "score_sum": np.ascontiguousarray(pileup["score_sum"], dtype=np.int64)}
+    for name in ("used", "partial", "long_", "weak"):
+        arrays[name] = np.ascontiguousarray(pileup[name], dtype=np.uint64)
+    total = int(arrays["col_off"][M])
+    if arrays["columns"].size != total * 6 or arrays["slots"].size != (total + M) * 5 or any(len(arrays[k]) != M for k in ("used", "partial", "long_", "weak", "score_sum")):
+        raise ValueError("the pileup's arrays do not have the sizes its col_off gives")
+    s = MonomerPileupC(n_templates=M)
+    for name, a in arrays.items():
+        setattr(s, name, a.ctypes.data_as(dict(MonomerPileupC._fields_)[name]))
+    return s, arrays
+
+
+def monomer_consensus(pileup, templates):
+    """cl_monomer_consensus (host only): the vote of a monomer_pileup dict over `templates` as a dict of templates (str) and changed (bool) per
+    template (names None, rounds 0)"""
+    lib = load_library()
+    traw, tbufs, tlens = _strings(templates)
+    s, keep = _pileup_struct(pileup)
+    lib.cl_monomer_templates_free.argtypes = [C.POINTER(MonomerTemplatesC)]
+    lib.cl_monomer_templates_free.restype = None
+    out = MonomerTemplatesC()
+    lib.cl_monomer_consensus.argtypes = [C.POINTER(MonomerPileupC), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MonomerTemplatesC)]
+    rc = lib.cl_monomer_consensus(C.byref(s), tbufs, tlens.ctypes.data, len(traw), C.byref(out))
+    del keep
+    if rc != 0:
+        _raise_last(lib, rc)
+    return _templates_dict(lib, out)
+
+
+def _monomer_refine(ctx, sequences, templates, max_rounds, least_share, params):
+    lib = load_library()
+    raw, bufs, lens = _strings(sequences)
+    traw, tbufs, tlens = _strings(templates)
+    p = _monomers_params(lib, params)
+    lib.cl_monomer_templates_free.argtypes = [C.POINTER(MonomerTemplatesC)]
+    lib.cl_monomer_templates_free.restype = None
+    out = MonomerTemplatesC()
+    tail = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MonomersParams), C.c_uint32, C.c_uint32, C.POINTER(MonomerTemplatesC)]
+    args = (bufs, lens.ctypes.data, len(raw), tbufs, tlens.ctypes.data, len(traw), C.byref(p), int(least_share), int(max_rounds), C.byref(out))
+    if ctx is None:
+        h = None
+        lib.cl_monomer_templates_refine_host.argtypes = tail
+        rc = lib.cl_monomer_templates_refine_host(*args)
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_monomer_templates_refine_compute.argtypes = [C.c_void_p] + tail
+        rc = lib.cl_monomer_templates_refine_compute(h, *args)
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    return _templates_dict(lib, out)
+
+
+def monomer_templates_refine_host(sequences, templates, max_rounds=8, least_share=0, **params):
+    """cl_monomer_templates_refine_host (host only): up to `max_rounds` rounds of decompose, pile up, vote from `templates`: a dict of templates,
+    changed (against the ones given), rounds, converged and round (per round blocks, used, changed and the four device times)"""
+    return _monomer_refine(None, sequences, templates, max_rounds, least_share, params)
+
+
+def monomer_templates_refine(ctx, sequences, templates, max_rounds=8, least_share=0, **params):
+    """cl_monomer_templates_refine_compute: the same on the device, byte for byte but the times"""
+    if ctx is None:
+        raise ValueError("monomer_templates_refine needs a context (monomer_templates_refine_host is the host call)")
+    return _monomer_refine(ctx, sequences, templates, max_rounds, least_share, params)
+
+
+def monomer_seed_templates(sequences, period, count=1, start=0, strands=1, _lengths=None):
+    """cl_monomer_seed_templates (host only): `count` pieces of `period` bases from base `start` of the first sequence, named seed1 .. seedK"""
+    lib = load_library()
+    raw, bufs, lens = _strings(sequences)
+    if _lengths is not None:
+        lens = np.array([int(x) for x in _lengths], dtype=np.uint64)
+    lib.cl_monomer_templates_free.argtypes = [C.POINTER(MonomerTemplatesC)]
+    lib.cl_monomer_templates_free.restype = None
+    out = MonomerTemplatesC()
+    lib.cl_monomer_seed_templates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(MonomerTemplatesC)]
+    rc = lib.cl_monomer_seed_templates(bufs, lens.ctypes.data, len(raw), int(period), int(count), int(start), int(strands), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc)
+    return _templates_dict(lib, out)
+
+
+def _text_result(lib, rc, text, ln):
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return C.string_at(text.value, ln.value)
+    finally:
+        _libc_free(text)
+
+
+def monomer_pileup_tsv(pileup, template_names, templates):
+    """cl_monomer_pileup_tsv (host only): one row per column and end slot of a monomer_pileup dict as bytes"""
+    lib = load_library()
+    _, narr, _ = _strings(template_names)
+    traw, tbufs, tlens = _strings(templates)
+    if len(template_names) != len(traw):
+        raise ValueError("%d names for %d templates" % (len(template_names), len(traw)))
+    s, keep = _pileup_struct(pileup)
+    lib.cl_monomer_pileup_tsv.argtypes = [C.POINTER(MonomerPileupC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = lib.cl_monomer_pileup_tsv(C.byref(s), narr, tbufs, tlens.ctypes.data, len(traw), C.byref(text), C.byref(ln))
+    del keep
+    return _text_result(lib, rc, text, ln)
+
+
+def monomer_templates_fasta(names, templates):
+    """cl_monomer_templates_fasta (host only): `>name` and the bases on one line per template, as bytes"""
+    lib = load_library()
+    _, narr, _ = _strings(names)
+    traw, tbufs, tlens = _strings(templates)
+    if len(names) != len(traw):
+        raise ValueError("%d names for %d templates" % (len(names), len(traw)))
+    lib.cl_monomer_templates_fasta.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    text, ln = C.c_void_p(), C.c_uint64()
+    rc = lib.cl_monomer_templates_fasta(narr, tbufs, tlens.ctypes.data, len(traw), C.byref(text), C.byref(ln))
+    return _text_result(lib, rc, text, ln)
+
+
 def neighbor_joining_newick(distance, names):
     """cl_neighbor_joining_newick (host only): the midpoint-rooted neighbor-joining tree of an [n, n] distance matrix as Newick text"""
     lib = load_library()
@@ -2066,6 +2289,8 @@ EXPORTED_SYMBOLS = [
     "cl_period_spectrum_free",
     "cl_monomers_params_default", "cl_monomer_decompose_host", "cl_monomer_decompose_compute", "cl_monomers_tsv", "cl_monomers_summary_tsv",
     "cl_monomer_decomposition_free",
+    "cl_monomer_pileup_host", "cl_monomer_pileup_compute", "cl_monomer_pileup_free", "cl_monomer_consensus", "cl_monomer_templates_refine_host",
+    "cl_monomer_templates_refine_compute", "cl_monomer_templates_free", "cl_monomer_seed_templates", "cl_monomer_pileup_tsv", "cl_monomer_templates_fasta",
 ]
 
 

@@ -21,6 +21,9 @@
 //     options) before the alignment starts; --periods-only ends the run there;
 //   - --monomers FILE with --monomers-templates FASTA writes which monomer stands where on every input sequence (cl_monomer_decompose_compute;
 //     --monomers-summary and the --monomers-* options) before the alignment starts; --monomers-only ends the run there;
+//   - --monomers-rounds N refines the templates first (cl_monomer_templates_refine_compute), --monomers-seed-period cuts them from the first
+//     sequence instead of reading them, --monomers-write-templates and --monomers-pileup write the final templates and the per-column counts
+//     under them (cl_monomer_pileup_compute);
 //   - -v gates this tool's own progress lines; the device is opened only when the alignment starts.
 #include <getopt.h>
 
@@ -507,14 +510,58 @@ bool read_monomer_templates(const std::string& file, int strands, MonomerTemplat
     return true;
 }
 
-bool write_monomers(cl_context* ctx, const std::string& fasta_text, const MonomerTemplates& t, const cl_monomers_params& params, const std::string& file,
-                    const std::string& summary_file, std::string& err) {
+// --monomers-rounds, --monomers-least-share, --monomers-write-templates, --monomers-pileup
+struct MonomerRefinement {
+    uint32_t rounds = 0, least_share = 0;
+    std::string templates_file, pileup_file;
+};
+
+bool write_text_file(const std::string& to, const char* text, uint64_t len) {
+    FILE* f = fopen(to.c_str(), "wb");
+    const bool written = f && fwrite(text, 1, len, f) == len;
+    return !((f && fclose(f) != 0) || !written);
+}
+
+bool write_monomers(cl_context* ctx, const std::string& fasta_text, const MonomerTemplates& given, const cl_monomers_params& params, const MonomerRefinement& refinement,
+                    const std::string& file, const std::string& summary_file, std::string& err) {
     cl_fasta fa;
     if (cl_parse_fasta(nullptr, fasta_text.data(), fasta_text.size(), &fa)) { err = lib_error(); return false; }
     struct FreeFasta { cl_fasta* f; ~FreeFasta() { cl_fasta_free(f); } } free_fasta{&fa};
     std::vector<std::string> shown(fa.names, fa.names + fa.n_sequences);
     std::vector<const char*> names;
     for (std::string& nm : shown) { std::replace(nm.begin(), nm.end(), '/', '_'); names.push_back(nm.c_str()); }
+    MonomerTemplates t = given;   // the final templates: the given ones unless rounds are asked for
+    char line[320];
+    if (refinement.rounds) {
+        cl_monomer_templates refined;
+        if (cl_monomer_templates_refine_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, given.base_ptr.data(), given.lengths.data(), given.lengths.size(), &params,
+                                                refinement.least_share, refinement.rounds, &refined)) {
+            const char* e = cl_last_error(ctx);
+            err = std::string("the template refinement: ") + (e && *e ? e : "failed");
+            return false;
+        }
+        for (uint32_t r = 0; r < refined.rounds; ++r) {
+            const cl_monomer_round& q = refined.round[r];
+            snprintf(line, sizeof(line), "Template round %u: %llu blocks, %llu used, %llu templates changed; rows %.3f ms, blocks %.3f ms, alignments %.3f ms, counts %.3f ms on the device.",
+                     r + 1, (unsigned long long)q.blocks, (unsigned long long)q.used, (unsigned long long)q.changed, q.dp_ms, q.trace_ms, q.align_ms, q.count_ms);
+            log_line(LOG_VERBOSE, line);
+        }
+        snprintf(line, sizeof(line), "The templates %s after %u round(s).", refined.converged ? "converged" : "did not converge", refined.rounds);
+        log_line(LOG_VERBOSE, line);
+        for (size_t m = 0; m < t.bases.size(); ++m) { t.bases[m].assign(refined.templates[m], refined.lengths[m]); t.lengths[m] = refined.lengths[m]; }
+        cl_monomer_templates_free(&refined);
+    }
+    t.name_ptr.clear();
+    t.base_ptr.clear();
+    for (size_t m = 0; m < t.names.size(); ++m) { t.name_ptr.push_back(t.names[m].c_str()); t.base_ptr.push_back(t.bases[m].c_str()); }
+    if (!refinement.templates_file.empty()) {
+        char* text = nullptr;
+        uint64_t len = 0;
+        if (cl_monomer_templates_fasta(t.name_ptr.data(), t.base_ptr.data(), t.lengths.data(), t.lengths.size(), &text, &len)) { err = "the templates: " + lib_error(); return false; }
+        const bool written = write_text_file(refinement.templates_file, text, len);
+        free(text);
+        if (!written) { err = "could not write the templates to " + refinement.templates_file; return false; }
+    }
     cl_monomer_decomposition dec;
     if (cl_monomer_decompose_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, t.base_ptr.data(), t.lengths.data(), t.lengths.size(), &params, &dec)) {
         const char* e = cl_last_error(ctx);
@@ -522,10 +569,31 @@ bool write_monomers(cl_context* ctx, const std::string& fasta_text, const Monome
         return false;
     }
     struct FreeDecomposition { cl_monomer_decomposition* d; ~FreeDecomposition() { cl_monomer_decomposition_free(d); } } free_decomposition{&dec};
-    char line[256];
     snprintf(line, sizeof(line), "The monomer decomposition: %llu problems, %llu blocks; rows %.3f ms, blocks %.3f ms on the device.",
              (unsigned long long)dec.n_problems, (unsigned long long)dec.n_blocks, dec.dp_ms, dec.trace_ms);
     log_line(LOG_VERBOSE, line);
+    if (!refinement.pileup_file.empty()) {
+        cl_monomer_pileup pile;
+        if (cl_monomer_pileup_compute(ctx, fa.sequences, fa.lengths, fa.n_sequences, t.base_ptr.data(), t.lengths.data(), t.lengths.size(), &params, &dec,
+                                      refinement.least_share, &pile)) {
+            const char* e = cl_last_error(ctx);
+            err = std::string("the monomer pileup: ") + (e && *e ? e : "failed");
+            return false;
+        }
+        uint64_t used = 0;
+        for (uint64_t m = 0; m < pile.n_templates; ++m) used += pile.used[m];
+        snprintf(line, sizeof(line), "The monomer pileup: %llu blocks used; alignments %.3f ms, counts %.3f ms on the device.", (unsigned long long)used, pile.align_ms,
+                 pile.count_ms);
+        log_line(LOG_VERBOSE, line);
+        char* text = nullptr;
+        uint64_t len = 0;
+        const int rc = cl_monomer_pileup_tsv(&pile, t.name_ptr.data(), t.base_ptr.data(), t.lengths.data(), t.lengths.size(), &text, &len);
+        cl_monomer_pileup_free(&pile);
+        if (rc) { err = "the monomer pileup: " + lib_error(); return false; }
+        const bool written = write_text_file(refinement.pileup_file, text, len);
+        free(text);
+        if (!written) { err = "could not write the monomer pileup to " + refinement.pileup_file; return false; }
+    }
     for (int which = 0; which < 2; ++which) {
         const std::string& to = which == 0 ? file : summary_file;
         if (to.empty()) continue;
@@ -618,6 +686,13 @@ void print_help(const cl_config* defaults) {
     fprintf(o, " --monomers-chunk INT        With --monomers, the bases of a sequence that are decomposed at once, 64 to 1048576, or 0 for all of them [4096]\n");
     fprintf(o, " --monomers-overlap INT      With --monomers, the bases a chunk reads beyond either end, 0 to 1048576; two template lengths or more [512]\n");
     fprintf(o, " --monomers-only             With --monomers, end after writing the decomposition: nothing is aligned or printed\n");
+    fprintf(o, " --monomers-rounds INT       With --monomers, refine the templates in up to INT rounds (1 to 64) of decompose, align, vote before the decomposition is written\n");
+    fprintf(o, " --monomers-write-templates FASTA  With --monomers-rounds or seeds, write the final templates to FASTA (which must not exist yet)\n");
+    fprintf(o, " --monomers-pileup FILE      With --monomers, write the per-column base counts of the blocks under the final templates to FILE (which must not exist yet)\n");
+    fprintf(o, " --monomers-least-share INT  With --monomers, the per mille of match * length a block's score must reach to be counted, 0 to 1000 [0]\n");
+    fprintf(o, " --monomers-seed-period INT  With --monomers, cut the templates from the first sequence, INT bases each (1 to 1024), instead of --monomers-templates\n");
+    fprintf(o, " --monomers-seed-count INT   With --monomers-seed-period, the number of templates cut [1]\n");
+    fprintf(o, " --monomers-seed-start INT   With --monomers-seed-period, the base of the first sequence at which the first template begins [0]\n");
     fprintf(o, " --help / -h                 Print this message and exit\n");
     fprintf(o, "\n");
     fprintf(o, "Differences from the reference centrolign: every failure is 'error: ...' with exit status 1; -p takes a decimal number;\n");
@@ -626,8 +701,9 @@ void print_help(const cl_config* defaults) {
     fprintf(o, "--site-min-minor, --site-max-gaps, --dotplot, --dotplot-k, --dotplot-window, --dotplot-min-identity, --dotplot-pairs, --dotplot-only,\n");
     fprintf(o, "--periods, --periods-hist, --periods-k, --periods-window, --periods-max, --periods-peaks, --periods-radius, --periods-min-period,\n");
     fprintf(o, "--periods-min-count, --periods-scope, --periods-only, --monomers, --monomers-templates, --monomers-summary, --monomers-strands,\n");
-    fprintf(o, "--monomers-match, --monomers-mismatch, --monomers-insertion, --monomers-deletion, --monomers-chunk, --monomers-overlap and\n");
-    fprintf(o, "--monomers-only are added; -v gates this tool's own progress lines. See README.md.\n");
+    fprintf(o, "--monomers-match, --monomers-mismatch, --monomers-insertion, --monomers-deletion, --monomers-chunk, --monomers-overlap,\n");
+    fprintf(o, "--monomers-only, --monomers-rounds, --monomers-write-templates, --monomers-pileup, --monomers-least-share, --monomers-seed-period,\n");
+    fprintf(o, "--monomers-seed-count and --monomers-seed-start are added; -v gates this tool's own progress lines. See README.md.\n");
 }
 
 struct Owned {
@@ -664,6 +740,8 @@ int run(int argc, char** argv) {
     std::string monomers_arg[6];   // --monomers-match, -mismatch, -insertion, -deletion, -chunk, -overlap as given
     bool have_monomers_arg[6] = {false, false, false, false, false, false}, have_monomers_strands = false, monomers_only = false;
     bool beside_monomers_only = false;   // an option --monomers-only does not go with
+    std::string monomers_more[7];   // --monomers-rounds, -write-templates, -pileup, -least-share, -seed-period, -seed-count, -seed-start as given
+    bool have_monomers_more[7] = {false, false, false, false, false, false, false};
     std::vector<int> devices;
 
     enum { OPT_SKIP_CALIBRATION = 1000, OPT_FORCE_GFA_OUTPUT = 1001, OPT_BOND_PREFIX = 1003, OPT_DEVICES = 1004, OPT_INFER_TREE = 1005, OPT_TREE_OUT = 1006,
@@ -676,7 +754,8 @@ int run(int argc, char** argv) {
            OPT_PERIODS_RADIUS = 1035, OPT_PERIODS_MIN_PERIOD = 1036, OPT_PERIODS_MIN_COUNT = 1037, OPT_PERIODS_SCOPE = 1038, OPT_PERIODS_ONLY = 1039,
            OPT_MONOMERS = 1040, OPT_MONOMERS_TEMPLATES = 1041, OPT_MONOMERS_SUMMARY = 1042, OPT_MONOMERS_STRANDS = 1043, OPT_MONOMERS_MATCH = 1044,
            OPT_MONOMERS_MISMATCH = 1045, OPT_MONOMERS_INSERTION = 1046, OPT_MONOMERS_DELETION = 1047, OPT_MONOMERS_CHUNK = 1048, OPT_MONOMERS_OVERLAP = 1049,
-           OPT_MONOMERS_ONLY = 1050 };
+           OPT_MONOMERS_ONLY = 1050, OPT_MONOMERS_ROUNDS = 1051, OPT_MONOMERS_WRITE_TEMPLATES = 1052, OPT_MONOMERS_PILEUP = 1053, OPT_MONOMERS_LEAST_SHARE = 1054,
+           OPT_MONOMERS_SEED_PERIOD = 1055, OPT_MONOMERS_SEED_COUNT = 1056, OPT_MONOMERS_SEED_START = 1057 };
     static const struct option options[] = {
         {"tree", required_argument, nullptr, 'T'},
         {"all-pairs", required_argument, nullptr, 'A'},
@@ -745,6 +824,13 @@ int run(int argc, char** argv) {
         {"monomers-chunk", required_argument, nullptr, OPT_MONOMERS_CHUNK},
         {"monomers-overlap", required_argument, nullptr, OPT_MONOMERS_OVERLAP},
         {"monomers-only", no_argument, nullptr, OPT_MONOMERS_ONLY},
+        {"monomers-rounds", required_argument, nullptr, OPT_MONOMERS_ROUNDS},
+        {"monomers-write-templates", required_argument, nullptr, OPT_MONOMERS_WRITE_TEMPLATES},
+        {"monomers-pileup", required_argument, nullptr, OPT_MONOMERS_PILEUP},
+        {"monomers-least-share", required_argument, nullptr, OPT_MONOMERS_LEAST_SHARE},
+        {"monomers-seed-period", required_argument, nullptr, OPT_MONOMERS_SEED_PERIOD},
+        {"monomers-seed-count", required_argument, nullptr, OPT_MONOMERS_SEED_COUNT},
+        {"monomers-seed-start", required_argument, nullptr, OPT_MONOMERS_SEED_START},
         {nullptr, 0, nullptr, 0},
     };
     opterr = 0;   // reported here, as "error: ..."
@@ -755,7 +841,7 @@ int run(int argc, char** argv) {
         const char* value = optarg;
         if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_DOTPLOT && o <= OPT_DOTPLOT_ONLY)) beside_dotplot_only = true;
         if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_PERIODS && o <= OPT_PERIODS_ONLY)) beside_periods_only = true;
-        if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_MONOMERS && o <= OPT_MONOMERS_ONLY)) beside_monomers_only = true;
+        if (o != 'v' && o != OPT_DEVICES && !(o >= OPT_MONOMERS && o <= OPT_MONOMERS_SEED_START)) beside_monomers_only = true;
         switch (o) {
         case 'T': name = "tree_name"; break;
         case 'A': name = "all_pairs_prefix"; break;
@@ -823,6 +909,11 @@ int run(int argc, char** argv) {
             have_monomers_arg[o - OPT_MONOMERS_MATCH] = true;
             break;
         case OPT_MONOMERS_ONLY: monomers_only = true; break;
+        case OPT_MONOMERS_ROUNDS: case OPT_MONOMERS_WRITE_TEMPLATES: case OPT_MONOMERS_PILEUP: case OPT_MONOMERS_LEAST_SHARE: case OPT_MONOMERS_SEED_PERIOD:
+        case OPT_MONOMERS_SEED_COUNT: case OPT_MONOMERS_SEED_START:
+            monomers_more[o - OPT_MONOMERS_ROUNDS] = optarg;
+            have_monomers_more[o - OPT_MONOMERS_ROUNDS] = true;
+            break;
         case ':':
         default: {
             // optopt names a short option; a long one is the argument getopt just stepped over
@@ -960,16 +1051,26 @@ int run(int argc, char** argv) {
     cl_monomers_params monomers_params;
     cl_monomers_params_default(&monomers_params);
     MonomerTemplates monomer_templates;
+    MonomerRefinement monomer_refinement;
+    uint64_t monomer_seed[3] = {0, 1, 0};   // period (0: no seeds), count, start
     {
         static const char* const opts[6] = {"--monomers-match", "--monomers-mismatch", "--monomers-insertion", "--monomers-deletion", "--monomers-chunk", "--monomers-overlap"};
+        static const char* const more_opts[7] = {"--monomers-rounds", "--monomers-write-templates", "--monomers-pileup", "--monomers-least-share", "--monomers-seed-period",
+                                                 "--monomers-seed-count", "--monomers-seed-start"};
         if (monomers.empty()) {
             const char* lone = !monomers_templates.empty() ? "--monomers-templates" : !monomers_summary.empty() ? "--monomers-summary"
                                : have_monomers_strands ? "--monomers-strands" : monomers_only ? "--monomers-only" : nullptr;
             for (int i = 5; i >= 0; --i) if (have_monomers_arg[i]) lone = opts[i];
+            for (int i = 6; i >= 0; --i) if (have_monomers_more[i]) lone = more_opts[i];
             if (lone) return fail(std::string(lone) + " needs --monomers");
         } else {
             if (have_graph) return fail("--monomers cannot be combined with --graph: it reads the sequences of a FASTA");
-            if (monomers_templates.empty()) return fail("--monomers needs --monomers-templates");
+            if (monomers_templates.empty() && !have_monomers_more[4]) return fail("--monomers needs --monomers-templates or --monomers-seed-period");
+            if (!monomers_templates.empty() && have_monomers_more[4]) return fail("--monomers-templates and --monomers-seed-period cannot both be given");
+            if (!have_monomers_more[4] && (have_monomers_more[5] || have_monomers_more[6]))
+                return fail(std::string(have_monomers_more[5] ? more_opts[5] : more_opts[6]) + " needs --monomers-seed-period");
+            if (have_monomers_more[1] && !have_monomers_more[0] && !have_monomers_more[4])
+                return fail("--monomers-write-templates needs --monomers-rounds or --monomers-seed-period: the given templates would be written back");
             uint64_t v = 0;
             if (have_monomers_arg[0] && (!parse_positive(monomers_arg[0], v) || v > 64)) return fail("--monomers-match expects a score from 1 to 64, got '" + monomers_arg[0] + "'");
             if (have_monomers_arg[0]) monomers_params.match = (int32_t)v;
@@ -1001,9 +1102,43 @@ int run(int argc, char** argv) {
             for (const std::string& other : others)
                 if (!other.empty() && (monomers == other || monomers_summary == other))
                     return fail("--monomers and --monomers-summary cannot name the file of another output option");
-            if (monomers == monomers_templates || monomers_summary == monomers_templates) return fail("--monomers and --monomers-summary cannot name the templates' file");
+            if (!monomers_templates.empty() && (monomers == monomers_templates || monomers_summary == monomers_templates))
+                return fail("--monomers and --monomers-summary cannot name the templates' file");
+            if (have_monomers_more[0]) {
+                if (!parse_positive(monomers_more[0], v) || v > 64) return fail("--monomers-rounds expects a whole number of rounds from 1 to 64, got '" + monomers_more[0] + "'");
+                monomer_refinement.rounds = (uint32_t)v;
+            }
+            if (have_monomers_more[3]) {
+                if (!parse_count(monomers_more[3], v) || v > 1000) return fail("--monomers-least-share expects a whole number of per mille from 0 to 1000, got '" + monomers_more[3] + "'");
+                monomer_refinement.least_share = (uint32_t)v;
+            }
+            if (have_monomers_more[4]) {
+                if (!parse_positive(monomers_more[4], v) || v > 1024) return fail("--monomers-seed-period expects a whole number of bases from 1 to 1024, got '" + monomers_more[4] + "'");
+                monomer_seed[0] = v;
+                if (have_monomers_more[5] && (!parse_positive(monomers_more[5], v) || v > 8192))
+                    return fail("--monomers-seed-count expects a whole number of templates from 1 on, got '" + monomers_more[5] + "'");
+                if (have_monomers_more[5]) monomer_seed[1] = v;
+                if (monomer_seed[0] * monomer_seed[1] * (uint64_t)monomers_params.strands > 8192)
+                    return fail("--monomers-seed-count: " + std::to_string(monomer_seed[1]) + " templates of " + std::to_string(monomer_seed[0]) +
+                                " bases are more than 8192 template bases in all (both strands counted)");
+                if (have_monomers_more[6] && (!parse_count(monomers_more[6], v) || v >= (1ull << 30)))
+                    return fail("--monomers-seed-start expects a whole number of bases below 2^30, got '" + monomers_more[6] + "'");
+                if (have_monomers_more[6]) monomer_seed[2] = v;
+            }
+            monomer_refinement.templates_file = monomers_more[1];
+            monomer_refinement.pileup_file = monomers_more[2];
+            for (int i = 1; i <= 2; ++i) {
+                const std::string& made = monomers_more[i];
+                if (!have_monomers_more[i]) continue;
+                if (made.empty()) return fail(std::string(more_opts[i]) + " expects a file name");
+                if (std::ifstream(made).good()) return fail(std::string(i == 1 ? "Monomer templates" : "Monomer pileup") + " file already exists: " + made);
+                if (made == monomers || made == monomers_summary || made == monomers_templates || (i == 2 && made == monomers_more[1]))
+                    return fail(std::string(more_opts[i]) + " cannot name the file of another --monomers option");
+                for (const std::string& other : others)
+                    if (made == other) return fail(std::string(more_opts[i]) + " cannot name the file of another output option");
+            }
             std::string err;
-            if (!read_monomer_templates(monomers_templates, monomers_params.strands, monomer_templates, err)) return fail(err);
+            if (!monomers_templates.empty() && !read_monomer_templates(monomers_templates, monomers_params.strands, monomer_templates, err)) return fail(err);
         }
     }
     // the tree options of this project, checked before anything is read or opened
@@ -1129,6 +1264,25 @@ int run(int argc, char** argv) {
     const std::vector<std::string> sequence_names(fa.names, fa.names + fa.n_sequences);
     uint64_t n_bases = 0;
     for (uint64_t i = 0; i < fa.n_sequences; ++i) n_bases += fa.lengths[i];
+    if (monomer_seed[0]) {   // the templates of --monomers-seed-period: pieces of the first sequence
+        cl_monomer_templates seeds;
+        if (cl_monomer_seed_templates(fa.sequences, fa.lengths, fa.n_sequences, (uint32_t)monomer_seed[0], (uint32_t)monomer_seed[1], monomer_seed[2],
+                                      monomers_params.strands, &seeds)) {
+            const std::string why = lib_error();
+            cl_fasta_free(&fa);
+            return fail("--monomers-seed-period: " + why);
+        }
+        for (uint64_t m = 0; m < seeds.n_templates; ++m) {
+            monomer_templates.names.push_back(seeds.names[m]);
+            monomer_templates.bases.push_back(std::string(seeds.templates[m], seeds.lengths[m]));
+            monomer_templates.lengths.push_back(seeds.lengths[m]);
+        }
+        for (size_t m = 0; m < monomer_templates.names.size(); ++m) {
+            monomer_templates.name_ptr.push_back(monomer_templates.names[m].c_str());
+            monomer_templates.base_ptr.push_back(monomer_templates.bases[m].c_str());
+        }
+        cl_monomer_templates_free(&seeds);
+    }
     cl_fasta_free(&fa);
     if (!dotplot.empty() && n_bases >= (1ull << 30)) return fail("--dotplot takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
     if (!periods.empty() && n_bases >= (1ull << 30)) return fail("--periods takes less than 2^30 bases, the input holds " + std::to_string(n_bases));
@@ -1137,7 +1291,7 @@ int run(int argc, char** argv) {
         if (n_sequences < 1) return fail("FASTA input from " + (fasta_name == "-" ? std::string("STDIN") : fasta_name) + " contains no sequence");
         own.ctx = cl_context_create(devices.empty() ? 0 : devices[0]);
         if (!own.ctx) return fail("no usable GPU: " + lib_error());
-        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomers, monomers_summary, err)) return fail(err);
+        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomer_refinement, monomers, monomers_summary, err)) return fail(err);
         log_line(LOG_MINIMAL, "Wrote the monomer decomposition to " + monomers + ", exiting.");
         return 0;
     }
@@ -1203,7 +1357,7 @@ int run(int argc, char** argv) {
     }
     if (!monomers.empty()) {
         log_line(LOG_BASIC, "Writing the monomer decomposition.");
-        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomers, monomers_summary, err)) return fail(err);
+        if (!write_monomers(own.ctx, fasta_text, monomer_templates, monomers_params, monomer_refinement, monomers, monomers_summary, err)) return fail(err);
     }
     if (infer_tree) {   // the tree goes to cl_msa exactly as the text of a -T file would
         log_line(LOG_BASIC, "Inferring a guide tree from k-mer distances.");

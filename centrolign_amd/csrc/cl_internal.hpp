@@ -427,6 +427,18 @@ struct ClMonomerProblem { uint64_t text_off, rec_off; uint32_t n, row0, keep_lo,
 int cl_monomers_device(cl_context* ctx, const char* const* seqs, const uint64_t* lens, uint64_t n, const std::vector<uint8_t>& codes,
                        const std::vector<uint32_t>& tmpl_off, const cl_monomers_params* p, const std::vector<ClMonomerProblem>& problems,
                        std::vector<cl_monomer_block>& blocks, float* dp_ms, float* trace_ms);
+// cl_monomers_api.cpp: every limit of the decomposition, for the calls that take the same arguments (cl_monomer_pileup_api.cpp)
+int cl_monomers_check_arguments(cl_context* ctx, const char* const* seqs, const uint64_t* lens, uint64_t n, const char* const* tmpl, const uint64_t* tmpl_len,
+                                uint64_t M, const cl_monomers_params* p, std::vector<uint8_t>& codes, std::vector<uint32_t>& tmpl_off);
+
+// monomer_pileup_kernels.hip: the used blocks of a validated decomposition (cl_monomer_pileup_api.cpp), ordered by forward template.  A block is n
+// bases from byte text_off of the sequences laid back to back, aligned to template `monomer` of codes / tmpl_off.  columns / slots: the counts in
+// the layout of cl_monomer_pileup (col_off: the forward templates' offsets); scores[b]: G[n][L] of used block b.
+struct ClPileupBlock { uint32_t text_off, n, monomer, seq; };
+int cl_monomer_pileup_device(cl_context* ctx, const char* const* seqs, const uint64_t* lens, uint64_t n, const std::vector<uint8_t>& codes,
+                             const std::vector<uint32_t>& tmpl_off, uint32_t M, const cl_monomers_params* p, const std::vector<ClPileupBlock>& blocks,
+                             uint32_t* columns, size_t n_columns, uint32_t* slots, size_t n_slots, std::vector<int32_t>& scores, float* align_ms,
+                             float* count_ms);
 
 // host-side parallel loop over [0, n): f(begin, end) on up to 32 threads (the reference is single-threaded; the host glue around the device
 // passes is not part of the compared arithmetic, every iteration writes its own outputs).  The threads come from ONE pool per process

@@ -209,6 +209,12 @@ int check_text_arguments(const cl_monomer_decomposition* d, const char* const* n
 
 }  // namespace
 
+int cl_monomers_check_arguments(cl_context* ctx, const char* const* seqs, const uint64_t* lens, uint64_t n, const char* const* tmpl, const uint64_t* tmpl_len,
+                                uint64_t M, const cl_monomers_params* p, std::vector<uint8_t>& codes, std::vector<uint32_t>& tmpl_off) {
+    std::vector<ClMonomerProblem> problems;
+    return check_arguments(ctx, seqs, lens, n, tmpl, tmpl_len, M, p, codes, tmpl_off, problems);
+}
+
 extern "C" {
 
 void cl_monomers_params_default(cl_monomers_params* params) {

@@ -1219,6 +1219,93 @@ int  cl_monomers_summary_tsv(const cl_monomer_decomposition* dec, const char* co
                              uint64_t* len_out /* may be NULL */);
 void cl_monomer_decomposition_free(cl_monomer_decomposition* out);
 
+/* --- monomer pileups, consensus and template refinement (the CLI's --monomers-rounds, --monomers-pileup, --monomers-seed-period) -----------------
+ * The other half of the annotation chain: given a decomposition, every block that is a whole copy is aligned base by base to its template, the
+ * copies vote per template column, and the vote becomes the next template.  This is the decompose -> consensus loop that HORmon-style pipelines
+ * run on the CPU.  Every number is an integer and nothing depends on scheduling.
+ * Used blocks.  A block of `dec` belongs to forward template m = monomer mod M.  It is counted in partial[m] if flags != 0; else in long_[m] if
+ *   end - start > 2 * len_m (it holds an insertion and is no copy); else in weak[m] if score * 1000 < least_share * match * len_m (64 bits;
+ *   least_share is per mille, 0..1000); else in used[m], and it takes part.
+ * Alignment.  A used block x[0 .. n) is aligned globally to template `monomer` (for monomer >= M the reverse complement of template m, the string
+ *   the decomposition used), with linear gaps and the decomposition's s(), insertion and deletion:
+ *     G[0][j] = j * deletion;  G[i][0] = i * insertion;  G[i][j] = max(G[i-1][j-1] + s(x[i-1], B[j-1]), G[i-1][j] + insertion, G[i][j-1] + deletion)
+ *   The walk back starts at (n, L) and takes at every cell the diagonal if it attains G, else the insertion, else the deletion.  |G| <= 64 * 3072.
+ *   For a block with flags = 0 from a decomposition under the same templates and scores, G[n][L] equals the block's score.
+ * Counts.  Every column of the template then holds one block base or none ("deleted"); every slot j = 0 .. L (in front of column j; slot L is
+ *   behind the last column) holds zero or more inserted bases, of which the first in sequence order is recorded.  For monomer >= M column j of
+ *   the reverse complement is column L - 1 - j of the forward template with the base complemented, slot j is slot L - j, and the recorded base
+ *   is the last inserted one in the block's order, complemented: the first in the forward template's order.  Bases are A, C, G, T or `other`
+ *   (any other character, its own complement).
+ * cl_monomer_pileup: col_off[M + 1] are the offsets of the templates' columns, total = col_off[M].  columns[(col_off[m] + j) * 6 + c], c = A, C,
+ *   G, T, other, deleted: the six add up to used[m] in every column of template m.  slots[(col_off[m] + m + j) * 5 + c], c = A, C, G, T, other,
+ *   j = 0 .. len_m.  score_sum[m]: the sum of G[n][L] over the used blocks.  align_ms / count_ms: device time by events of the alignment kernel
+ *   and of clearing and fetching the counts; 0 from the host call.
+ * Consensus (cl_monomer_consensus; host only).  For template m with d = used[m] > 0 walk c = 0 .. L: (1) if 2 * (sum of slot c) > d and one of
+ *   A, C, G, T was recorded there, emit the one with the largest count, ties to the first of ACGT; (2) if c = L stop; (3) if 2 * deleted > d drop
+ *   column c; (4) else let mx be the largest of its A, C, G, T counts: mx = 0 keeps the template's character as it is; if the template's own
+ *   base, case-folded, attains mx it is kept, written in upper case; else the first of ACGT that attains mx.  Several inserted bases in one slot
+ *   enter one base a round.  A template with d = 0, an empty result or a result of more than 1024 bases stays as it was.  changed[m] says
+ *   whether the string differs.
+ * Refinement (cl_monomer_templates_refine_*).  T = templates; for r = 1 .. max_rounds (1..64): decompose under T, pile up, T' = consensus; if
+ *   T' = T: converged, stop; T = T'.  It returns T, the rounds run, whether it converged, and per round the blocks, the used blocks, the templates
+ *   changed and (device call) the four device times.  A T' whose bases no longer fit the decomposition's limit of 8192 ends the loop with T,
+ *   not converged.  The host and the device call return the same bytes in every field but the times.
+ * Seeds (cl_monomer_seed_templates; host only).  period P in 1..1024, count K >= 1 with K * P * strands <= 8192, start: template k is bases
+ *   [start + k P, start + (k + 1) P) of the first sequence, named seed1 .. seedK.  Refused if there is no sequence, if it is shorter, or if a
+ *   piece holds no character of ACGTacgt.
+ * cl_monomer_pileup_tsv: host only.  A header line, then monomer position base A C G T other deleted ins_A ins_C ins_G ins_T ins_other,
+ *   tab-separated: one row per column and per template one more for the end slot (position = length, base `.`, column counts 0).  A row's ins_*
+ *   are those of the slot in front of it.  cl_monomer_templates_fasta: `>name` and the bases on one line, per template.
+ * Limits: those of the decomposition, checked before a base is read; a `dec` whose blocks do not fit the sequences or templates (a sequence
+ *   index >= n, a monomer index >= strands * M, an end beyond the sequence, start > end) is CL_ERR_INVALID_ARGUMENT with a cl_last_error that
+ *   names the argument, never a fault.
+ * The arrays of a cl_monomer_pileup and of a cl_monomer_templates are malloc'ed: release them with the _free of each. */
+typedef struct cl_monomer_pileup {
+    uint64_t  n_templates;
+    uint64_t* col_off;                          /* [n_templates + 1] */
+    uint32_t* columns;                          /* [total * 6] */
+    uint32_t* slots;                            /* [(total + n_templates) * 5] */
+    uint64_t *used, *partial, *long_, *weak;    /* [n_templates] each */
+    int64_t*  score_sum;                        /* [n_templates] */
+    float     align_ms, count_ms;               /* device time by events */
+} cl_monomer_pileup;
+typedef struct cl_monomer_round {   /* 40 bytes */
+    uint64_t blocks, used, changed;
+    float    dp_ms, trace_ms, align_ms, count_ms;
+} cl_monomer_round;
+typedef struct cl_monomer_templates {
+    uint64_t  n_templates;
+    char**    templates;            /* [n_templates], each NUL-terminated */
+    uint64_t* lengths;              /* [n_templates] */
+    uint8_t*  changed;              /* [n_templates]: 1 where the string differs from the one given */
+    char**    names;                /* [n_templates] from cl_monomer_seed_templates, else NULL */
+    uint32_t  rounds;               /* rounds run (refinement), else 0 */
+    int32_t   converged;
+    cl_monomer_round* round;        /* [rounds] */
+} cl_monomer_templates;
+int  cl_monomer_pileup_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const char* const* templates,
+                            const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params,
+                            const cl_monomer_decomposition* dec, uint32_t least_share, cl_monomer_pileup* out);
+int  cl_monomer_pileup_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, const char* const* templates,
+                               const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params,
+                               const cl_monomer_decomposition* dec, uint32_t least_share, cl_monomer_pileup* out);
+void cl_monomer_pileup_free(cl_monomer_pileup* out);
+int  cl_monomer_consensus(const cl_monomer_pileup* pileup, const char* const* templates, const uint64_t* template_lengths, uint64_t n_templates,
+                          cl_monomer_templates* out);
+int  cl_monomer_templates_refine_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const char* const* templates,
+                                      const uint64_t* template_lengths, uint64_t n_templates, const cl_monomers_params* params, uint32_t least_share,
+                                      uint32_t max_rounds, cl_monomer_templates* out);
+int  cl_monomer_templates_refine_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n,
+                                         const char* const* templates, const uint64_t* template_lengths, uint64_t n_templates,
+                                         const cl_monomers_params* params, uint32_t least_share, uint32_t max_rounds, cl_monomer_templates* out);
+void cl_monomer_templates_free(cl_monomer_templates* out);
+int  cl_monomer_seed_templates(const char* const* sequences, const uint64_t* lengths, uint64_t n, uint32_t period, uint32_t count, uint64_t start,
+                               int strands, cl_monomer_templates* out);
+int  cl_monomer_pileup_tsv(const cl_monomer_pileup* pileup, const char* const* template_names, const char* const* templates,
+                           const uint64_t* template_lengths, uint64_t n_templates, char** text_out, uint64_t* len_out /* may be NULL */);
+int  cl_monomer_templates_fasta(const char* const* names, const char* const* templates, const uint64_t* template_lengths, uint64_t n_templates,
+                                char** text_out, uint64_t* len_out /* may be NULL */);
+
 /* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
  * from.  Enums are integers.  Parameters are named as in the reference; a value is given and read back as config text (the same parsers
