@@ -513,11 +513,6 @@ int host_route_alignment(int route, const GraphView& g1, const GraphView& g2, in
 }
 
 // ---- the switches of plan creation ------------------------------------------------------------------------------------------------------
-// test hook: CL_FORCE_GENERAL=1 in the environment routes chain x chain problems to the general kernel too
-const bool g_force_general = [] { const char* e = getenv("CL_FORCE_GENERAL"); return e && *e == '1'; }();
-const bool g_no_sys = [] { const char* e = getenv("CL_NO_SYS"); return e && *e == '1'; }();     // test hook: no systolic DAG kernel
-const bool g_no_strip = [] { const char* e = getenv("CL_NO_STRIP"); return e && *e == '1'; }();   // test hook: no strips of rows for large branching pairs (popoa_strip_kernel)
-const bool g_no_ring = [] { const char* e = getenv("CL_NO_RING"); return e && *e == '1'; }();   // test hook: HBM-plane general kernel only
 constexpr uint64_t kSysLdsBytes = 159 * 1024;    // LDS a systolic-DAG workgroup may take (rings of every row + the column records)
 constexpr uint64_t kRingLdsBytes = 128 * 1024;  // LDS a general-kernel workgroup may take for its anti-diagonal ring (160 KB per CU); launches are split at 64 KB
 
@@ -547,6 +542,11 @@ struct PackSwitches {
     uint32_t lane_rw = 4;              // CL_LANE_WAVES (lane_round_waves)
     int duos = -1;                     // CL_LINEAR_DUOS (duos_forced)
     bool no_lane = false;              // CL_NO_LANE
+    // test hooks, read at every plan creation like CL_NO_LANE (tests switch them inside one process; bench.py sets CL_NO_STRIP in a child's environment)
+    bool force_general = false;        // CL_FORCE_GENERAL: chain x chain and near-chain pairs go to the DAG kernels too (choose_chain, choose_lane, fit_strips)
+    bool no_sys = false;               // CL_NO_SYS: no systolic DAG kernel (choose_sys)
+    bool no_strip = false;             // CL_NO_STRIP: no strips of rows for large pairs, popoa_strip_kernel (choose_chain, choose_lane, fit_strips)
+    bool no_ring = false;              // CL_NO_RING: HBM-plane general kernel only (choose_ring)
     uint8_t lin_mid = 4, lin_big = 0;  // CL_LINEAR_WAVES_MID, CL_LINEAR_WAVES_BIG (choose_chain)
     bool span = true;                  // CL_LINEAR_SPAN (choose_chain)
     bool lane_wide = false;            // CL_LANE_WIDE (choose_lane)
@@ -560,6 +560,11 @@ PackSwitches read_pack_switches(uint64_t n_problems) {
     sw.lane_rw = lane_round_waves(n_problems);
     sw.duos = duos_forced();
     sw.no_lane = no_lane_now();
+    auto is_one = [](const char* e) { return e && *e == '1'; };
+    sw.force_general = is_one(getenv("CL_FORCE_GENERAL"));
+    sw.no_sys = is_one(getenv("CL_NO_SYS"));
+    sw.no_strip = is_one(getenv("CL_NO_STRIP"));
+    sw.no_ring = is_one(getenv("CL_NO_RING"));
     auto waves_or = [](const char* e, int dflt) { const int v = e ? atoi(e) : 0; return (uint8_t)(v == 3 || v == 4 || v == 8 || v == 16 ? v : dflt); };
     sw.lin_mid = waves_or(getenv("CL_LINEAR_WAVES_MID"), 4);
     sw.lin_big = waves_or(getenv("CL_LINEAR_WAVES_BIG"), 0);
@@ -703,9 +708,9 @@ ChainChoice choose_chain(uint32_t n1, uint32_t n2, bool linear, const PackInput&
     const PackSwitches& sw = in.sw;
     ChainChoice c;
     const uint32_t nshort = std::min(n1, n2), nlong = std::max(n1, n2);
-    const bool span_linear = sw.span && linear && !g_force_general && nshort > 1024 && nshort <= 40000;
-    const bool big_linear = !span_linear && linear && !g_no_strip && !g_force_general && nshort >= 4096 && nshort <= 40000;
-    c.taken = linear && !g_force_general && !big_linear;
+    const bool span_linear = sw.span && linear && !sw.force_general && nshort > 1024 && nshort <= 40000;
+    const bool big_linear = !span_linear && linear && !sw.no_strip && !sw.force_general && nshort >= 4096 && nshort <= 40000;
+    c.taken = linear && !sw.force_general && !big_linear;
     if (!c.taken) return c;
     c.swap = n2 < n1;
     c.rows_per_lane = 1;
@@ -782,7 +787,7 @@ KernelChoice choose_lane(const PairView& V, const PackSwitches& sw) {
     const int sRow = V.sRow, sCol = V.sCol, npw = V.npw;
     const bool lane_wide = sw.lane_wide && n_rows > 193;
     const uint64_t lane_groups = lane_wide ? ((n_rows - 1 + 63) / 64 + 2) / 3 : 1;
-    if (sw.no_lane || g_force_general || lane_groups > 128 || !(lane_wide || n_rows - 1 <= sw.lane_max_rows) || (lane_wide && g_no_strip) || n_cols >= (1u << 28) || n_rows - 1 + n_cols < sw.lane_min_sweep) return c;
+    if (sw.no_lane || sw.force_general || lane_groups > 128 || !(lane_wide || n_rows - 1 <= sw.lane_max_rows) || (lane_wide && sw.no_strip) || n_cols >= (1u << 28) || n_rows - 1 + n_cols < sw.lane_min_sweep) return c;
     const uint32_t nR = (uint32_t)n_rows - 1, nCl = (uint32_t)n_cols;
     const uint32_t* rp = V.off[sRow];
     const uint8_t* rl = V.lab[sRow];
@@ -866,9 +871,9 @@ KernelChoice choose_lane(const PairView& V, const PackSwitches& sw) {
 // the systolic kernel (popoa_sys_kernel): the shorter graph's rows on the threads, a ring of H columns per row in LDS.  H must
 // exceed the row graph's predecessor span plus the column graph's NEAR predecessor distances; columns that are read from
 // further away (the fork in front of a long bubble; column 0 for a late source) are SAVED columns with LDS of their own
-KernelChoice choose_sys(const PairView& V) {
+KernelChoice choose_sys(const PairView& V, const PackSwitches& sw) {
     KernelChoice c;
-    if (g_no_sys || V.n_rows > 1024) return c;
+    if (sw.no_sys || V.n_rows > 1024) return c;
     const uint64_t n_rows = V.n_rows, n_cols = V.n_cols, n_pred = V.n_pred;
     const uint32_t* cp = V.off[V.sCol];   // node j (1-based rank): predecessors pidx[cp[j - 1] .. cp[j])
     uint64_t max_deg = 0;
@@ -906,7 +911,7 @@ StripFit fit_strips(const PairView& V, int sR, const PackSwitches& sw) {
     f.rows_side = sR;
     const int sC = 1 - sR;
     const uint64_t nRw = V.nodes(sR) + 1ull, nCl = V.nodes(sC);
-    if (g_no_strip || g_force_general || nRw < 192 || V.cells < 100000 || nCl >= (1u << 28)) return f;
+    if (sw.no_strip || sw.force_general || nRw < 192 || V.cells < 100000 || nCl >= (1u << 28)) return f;
     const uint32_t* cp = V.off[sC];
     const uint32_t* rp = V.off[sR];
     uint64_t max_deg = 0, gd = 0;
@@ -1027,14 +1032,14 @@ KernelChoice choose_strip(const PairView& V, const PackSwitches& sw, PackPart& P
 
 // LDS ring of the most recent anti-diagonals (popoa_kernels.hip): span1+span2+1 of them serve every read; when that
 // does not fit, as many as do (at least 8) — the rare reads that reach further back go to HBM.  Not taken: the general kernel with its planes in HBM
-KernelChoice choose_ring(const PairView& V) {
+KernelChoice choose_ring(const PairView& V, const PackSwitches& sw) {
     KernelChoice c;
     const uint64_t width = std::min(V.n1, V.n2) + 1, per_diag = width * (uint64_t)(1 + 2 * V.npw) * 4;
     // the ring variant also stages the subproblem's topology in LDS: offsets, predecessor ranks, labels
     const uint64_t topo_bytes = ((uint64_t)V.n1 + V.n2) * 8 + V.n_pred * 4 + ((uint64_t)V.n1 + V.n2 + 2) * (1 + V.npw) * 4 + 16;   // node records, lists, boundaries
     uint64_t depth = 1;   // a power of two (the kernel masks instead of dividing): enough for every read, or all that fits
     while (depth < V.span[0] + V.span[1] + 1 && 2 * depth * per_diag + topo_bytes <= kRingLdsBytes && depth < 16384) depth *= 2;
-    if (g_no_ring || depth * per_diag + topo_bytes > kRingLdsBytes || !(depth >= 8 || depth >= V.span[0] + V.span[1] + 1)) return c;
+    if (sw.no_ring || depth * per_diag + topo_bytes > kRingLdsBytes || !(depth >= 8 || depth >= V.span[0] + V.span[1] + 1)) return c;
     c.taken = true;
     c.pad = (uint16_t)(depth | (depth >= V.span[0] + V.span[1] + 1 ? 0x8000u : 0u));   // bit 15: the ring serves every read
     c.lds = depth * per_diag + topo_bytes;
@@ -1046,9 +1051,9 @@ KernelChoice choose_ring(const PairView& V) {
 void choose_dag_kernel(const PairView& V, const PackSwitches& sw, PackPart& P, ClProbDesc& d) {
     KernelChoice c = choose_lane(V, sw);
     if (c.taken) d.kind = CL_KIND_LANE;
-    else if ((c = choose_sys(V)).taken) d.kind = CL_KIND_SYS;
+    else if ((c = choose_sys(V, sw)).taken) d.kind = CL_KIND_SYS;
     else if ((c = choose_strip(V, sw, P)).taken) d.kind = CL_KIND_STRIP;
-    else c = choose_ring(V);   // (kind stays CL_KIND_GENERAL)
+    else c = choose_ring(V, sw);   // (kind stays CL_KIND_GENERAL)
     if (c.taken) d.pad = c.pad;
     if (d.kind != CL_KIND_GENERAL) {
         d.aux_base = (uint32_t)P.sys_aux.size();

@@ -9,3 +9,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_environment_table_is_current():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "env_switches.py"), "--check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
+
+
+def test_namespace_scope_constants_are_read_once():
+    """`const T g = [] { ... getenv ... }();` at namespace scope runs when the library is loaded, so the table must say `once` for it (CL_STITCH_GRAPH is spelt so);
+    the routing hooks that plan creation reads through read_pack_switches are `call`, which is what lets tests/test_gpu_general_kernels.py switch them in one process."""
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    try:
+        import env_switches
+    finally:
+        sys.path.pop(0)
+    found = env_switches.collect()
+    assert found["CL_STITCH_GRAPH"]["once"]
+    for name in ("CL_FORCE_GENERAL", "CL_NO_SYS", "CL_NO_STRIP", "CL_NO_RING", "CL_NO_LANE"):
+        assert not found[name]["once"], name
