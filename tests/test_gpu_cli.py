@@ -173,3 +173,32 @@ def test_gpu_cli_restart(tmp_path):
     loaded = [ln for ln in second.stderr.decode().split("\n") if "subproblem(s) from an earlier run" in ln]
     assert len(loaded) == 1 and int(loaded[0].split("Loaded ")[1].split()[0]) > 0
     assert sha((tmp_path / "sub.txt").read_bytes()) == SUB["sub_restart"]["files"]["sub.txt"]["sha256"]
+
+
+@pytest.mark.gpu
+def test_gpu_cli_all_outputs_in_one_run(tmp_path):
+    """one run that asks for the dot plot, the period spectra with their histogram, the monomer decomposition with its summary, the pair
+    statistics and the aligned FASTA at once: its files and its standard output are, byte for byte, those of runs that ask for each alone
+    (the --X-only runs for the three outputs that read the sequences).  Three sequences of about 3 kb under a balanced tree"""
+    names = ["seq%d" % i for i in range(3)]
+    seqs = synth.hor_sequences(11, 3000, 3, seq_div=0.01, hor_div=0.03, indel_hor=0)
+    one = tmp_path / "one"
+    one.mkdir()
+    fa, nwk = write_inputs(one, names, seqs, msa.newick(msa.balanced_tree(names)) + ";", wrap=80)
+    asked = {"dotplot": (["--dotplot", "dp.tsv"], ["dp.tsv"]),
+             "periods": (["--periods", "pe.tsv", "--periods-hist", "ph.tsv"], ["pe.tsv", "ph.tsv"]),
+             "monomers": (["--monomers", "mo.tsv", "--monomers-seed-period", 171, "--monomers-summary", "ms.tsv"], ["mo.tsv", "ms.tsv"]),
+             "pair-stats": (["--pair-stats", "ps.tsv"], ["ps.tsv"]),
+             "msa-out": (["--msa-out", "msa.fa"], ["msa.fa"])}
+    together = run(["-T", nwk, "-v", 0] + [a for args, _ in asked.values() for a in args] + [fa], one, timeout=120)
+    assert together.stdout.startswith(b"H\t") and together.stderr == b""
+    assert sorted(os.listdir(one)) == sorted(["in.fa", "t.nwk"] + [f for _, made in asked.values() for f in made])
+    for what, (args, made) in asked.items():
+        d = tmp_path / what
+        d.mkdir()
+        alone = what in ("pair-stats", "msa-out")   # the others have an --X-only run: nothing is aligned or printed
+        r = run((["-T", nwk] if alone else []) + ["-v", 0] + args + ([] if alone else ["--%s-only" % what]) + [fa], d, timeout=120)
+        assert r.stdout == (together.stdout if alone else b"") and r.stderr == b"", what
+        assert sorted(os.listdir(d)) == sorted(made), what
+        for f in made:
+            assert (d / f).read_bytes() == (one / f).read_bytes() and (d / f).stat().st_size > 0, (what, f)
