@@ -228,6 +228,29 @@ def stitch_rank_order(batch, k, side, mode="auto"):
     return order[:n], int(far.value), int(longest.value)
 
 
+class SysChoiceC(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("taken", "rows_are_graph2", "log2_depth", "near_limit", "near_max", "n_saved", "lds_bytes")]
+
+
+def stitch_sys_choice(batch, k, num_pw, mode="auto"):
+    """cl_stitch_sys_choice: what the packer's choose_sys decides for subproblem k at NumPW num_pw under the rank order `mode` (as stitch_rank_order), were the pair
+    offered to popoa_sys_kernel; no device needed.  Returns a dict: taken, rows_are_graph2, log2_depth, near_limit, near_max, saved (the saved columns,
+    ascending; 0 = the boundary column), lds_bytes — all 0 / empty where the pair is refused"""
+    lib = load_library()
+    bc = batch.as_c()
+    out, saved = SysChoiceC(), np.zeros(32, np.uint32)
+    lib.cl_stitch_sys_choice.restype = C.c_int
+    lib.cl_stitch_sys_choice.argtypes = [C.POINTER(StitchBatchC), C.c_uint64, C.c_int, C.c_int, C.POINTER(SysChoiceC), C.c_void_p]
+    rc = lib.cl_stitch_sys_choice(C.byref(bc), int(k), int(num_pw), {"auto": 0, "lifo": 1, "level": 2}[mode], C.byref(out), saved.ctypes.data)
+    if rc != 0:
+        raise ClError(rc, "cl_stitch_sys_choice")
+    d = {name: int(getattr(out, name)) for name, _ in SysChoiceC._fields_}
+    d["taken"] = bool(d["taken"])
+    d["rows_are_graph2"] = bool(d["rows_are_graph2"])
+    d["saved"] = [int(x) for x in saved[:d.pop("n_saved")]]
+    return d
+
+
 def partition_anchors(graph1, graph2, chain, score_scale=1.0, score_boundaries=False, use_annotated_score=False, **overrides):
     """Partitioner::partition_anchors (include/centrolign/partitioner.hpp:72-213), host only.  `chain` is the dict that
     Context.anchor_chain returns (walk_off, walk1, walk2, count1, count2, full_length, chain[:,0] = match set, score).
@@ -2041,7 +2064,7 @@ class StitchResult:
 
 
 _lib = None
-ABI_VERSION = 21    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
+ABI_VERSION = 22    # CL_ABI_VERSION of include/centrolign_amd.h these ctypes structures mirror
 
 
 def load_library(path=None):
@@ -2267,7 +2290,7 @@ EXPORTED_SYMBOLS = [
     "cl_read_gfa", "cl_subproblem_hash_hex", "cl_internal_fuse", "cl_induced_pairwise_cigar", "cl_induced_pairwise_cigars", "cl_induced_cyclic_maf",
     "cl_subalignment_text", "cl_bond_alignment_cigar",
     "cl_anchor_chain", "cl_anchor_chain_result_free", "cl_anchor_chain_masked", "cl_generate_diagonal_mask", "cl_update_mask", "cl_internal_stitch",
-    "cl_partition_params_default", "cl_partition_anchors", "cl_host_route_align", "cl_stitch_rank_order",
+    "cl_partition_params_default", "cl_partition_anchors", "cl_host_route_align", "cl_stitch_rank_order", "cl_stitch_sys_choice",
     "cl_core_align_params_default", "cl_core_align", "cl_core_align_result_free",
     "cl_split_params_default", "cl_split_branching_matches", "cl_owned_match_sets_view", "cl_owned_match_sets_free",
     "cl_estimate_score_scale", "cl_leaf_intrinsic_scale", "cl_leaf_graph", "cl_explicit_cigar", "cl_write_gfa",

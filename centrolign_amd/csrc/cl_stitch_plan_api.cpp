@@ -11,7 +11,7 @@
 // parts in order; form the launch groups, family by family; the persistent one-wave launch and the narrow launch over the group list; estimate and order;
 // upload and allocate.  Everything up to the upload is plain host code: the two device facts it needs (how many workgroups of the persistent / the narrow
 // kernel are resident at once) are handed in.  The plan is run by cl_stitch_exec_api.cpp; stitch_plan.hpp is what the two share.
-// Also here, with the helpers they share with the packer: the host-only entry points cl_host_route_align and cl_stitch_rank_order.
+// Also here, with the helpers they share with the packer: the host-only entry points cl_host_route_align, cl_stitch_rank_order and cl_stitch_sys_choice.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1848,6 +1848,45 @@ int cl_stitch_rank_order(const cl_stitch_batch* batch, uint64_t k, int side, int
     std::copy(order.begin(), order.end(), order_out);
     if (far_reads_out) *far_reads_out = far;
     if (longest_read_out) *longest_read_out = longest;
+    return CL_OK;
+}
+
+int cl_stitch_sys_choice(const cl_stitch_batch* batch, uint64_t k, int num_pw, int mode, cl_sys_choice* out, uint32_t* saved_out) {
+    if (!batch || k >= batch->n_problems || num_pw < 1 || num_pw > 3 || mode < 0 || mode > 2 || !out) return CL_ERR_INVALID_ARGUMENT;
+    *out = cl_sys_choice{};
+    const GraphView g[2] = {view(batch->side[0], k), view(batch->side[1], k)};
+    if (!g[0].n || !g[1].n || !g[0].n_src || !g[1].n_src) return CL_OK;   // (a pure deletion: no device launch)
+    // the pair packed into rank space exactly as pack_one packs it, into a part of its own
+    PackPart P;
+    Scratch S;
+    ClProbDesc d{};
+    d.n1 = (uint32_t)g[0].n; d.n2 = (uint32_t)g[1].n; d.npw = (uint8_t)num_pw;
+    bool linear = true;
+    uint64_t span[2] = {0, 0};
+    for (int s = 0; s < 2; ++s)
+        if (!pack_side(g[s], s, k, mode, P, S, d, span[s], linear)) return P.rc;
+    PairView V;
+    for (int s = 0; s < 2; ++s) { V.off[s] = P.poff[s].data() + d.node_base[s]; V.lab[s] = P.lab[s].data() + d.node_base[s]; V.pidx[s] = P.pidx[s].data(); V.span[s] = span[s]; }
+    V.n1 = d.n1; V.n2 = d.n2; V.npw = num_pw; V.cells = (g[0].n + 1) * (g[1].n + 1);
+    V.n_pred = (P.poff[0].back() - P.poff[0][d.node_base[0]]) + (P.poff[1].back() - P.poff[1][d.node_base[1]]);
+    V.sRow = d.n2 < d.n1 ? 1 : 0; V.sCol = 1 - V.sRow;
+    V.n_rows = std::min(d.n1, d.n2) + 1; V.n_cols = std::max(d.n1, d.n2);
+    const KernelChoice c = choose_sys(V, PackSwitches());
+    if (!c.taken) return CL_OK;
+    out->taken = 1;
+    out->rows_are_graph2 = c.pad >> 15;
+    out->log2_depth = c.pad & 31u;
+    out->near_limit = c.aux[0];
+    out->n_saved = c.aux_cnt;
+    out->lds_bytes = (uint32_t)c.lds;
+    // the farthest read the ring serves under that limit (a source's boundary column included), as the search counted it
+    const uint32_t* cp = V.off[V.sCol];
+    for (uint32_t j = 1; j <= V.n_cols; ++j) {
+        for (uint32_t e = cp[j - 1]; e < cp[j]; ++e)
+            if (j - V.pidx[V.sCol][e] <= out->near_limit) out->near_max = std::max(out->near_max, j - V.pidx[V.sCol][e]);
+        if ((V.lab[V.sCol][j - 1] & 0x80) && j <= out->near_limit) out->near_max = std::max(out->near_max, j);
+    }
+    if (saved_out) std::copy(c.aux.begin() + 1, c.aux.end(), saved_out);
     return CL_OK;
 }
 

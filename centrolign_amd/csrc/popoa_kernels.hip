@@ -689,7 +689,7 @@ __global__ void __launch_bounds__(BLOCK) popoa_ring_kernel(ClDeviceBatch B, cons
 // (p, q) for predecessors p of its row and q of its column — were finished (r - p), (c - q) and (r - p) + (c - q) steps earlier.  Every
 // row keeps its last H columns in an LDS ring, H a power of two above the row graph's predecessor span plus the column graph's NEAR
 // predecessor distances; a column that some later column reaches from further away (the fork in front of a bubble whose branches
-// differ by a whole repeat unit: one or two per subproblem) is a SAVED column: its cells are also written to a small LDS area of their
+// differ by a whole repeat unit, column 0 for a late source: a few per subproblem as a rule, 32 at the most) is a SAVED column: its cells are also written to a small LDS area of their
 // own ([slot][row]) and read from there.  So every read of the sweep is an LDS read, and — this is the point — the loop contains no
 // global load at all: on gfx9 loads and stores share one counter, a single load in the loop makes every step wait for the previous
 // step's plane stores (≈1 µs); without one the stores are fire-and-forget.  The row's own topology sits in registers, the column's

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 21 /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
+#define CL_ABI_VERSION 22 /* bumped whenever a struct layout or an entry point's signature changes; capi.py refuses a library of another version */
 
 /* AlignedPair::gap (src/alignment.cpp:11) */
 #define CL_GAP UINT64_MAX
@@ -291,6 +291,17 @@ int cl_host_route_align(const cl_stitch_batch* batch, uint64_t problem, const cl
  * order_out[rank] = local node id (n entries); the two counts describe the order returned.  Host only, no device needed. */
 int cl_stitch_rank_order(const cl_stitch_batch* batch, uint64_t problem, int side, int mode, uint32_t* order_out,
                          uint32_t* far_reads_out /* may be NULL */, uint32_t* longest_read_out /* may be NULL */);
+
+/* What the packer's choose_sys decides for one subproblem at a given NumPW (1-3) and rank order (mode as above), were the pair offered to the
+ * systolic DAG kernel (popoa_sys_kernel) — the families in front of it (chain, register kernel) are not asked: the rows side, the depth
+ * 2^log2_depth of every row's ring of columns, the near limit that won (column reads up to that far back come from the ring, near_max the
+ * farthest of them), the saved columns (ascending; 0 = the boundary column, saved for a late source) and the workgroup's dynamic LDS.
+ * Everything but `taken` is 0 where the pair is refused.  saved_out takes up to 32 entries.  Host only, no device needed. */
+typedef struct cl_sys_choice {
+    uint32_t taken, rows_are_graph2, log2_depth, near_limit, near_max, n_saved, lds_bytes;
+} cl_sys_choice;
+int cl_stitch_sys_choice(const cl_stitch_batch* batch, uint64_t problem, int num_pw, int mode, cl_sys_choice* out,
+                         uint32_t* saved_out /* may be NULL */);
 
 /* --- Stitcher::stitch proper: from a partitioned anchor chain to the stitched base-level alignment ----------------
  * (include/centrolign/stitcher.hpp:34-38,104-206).  The two merge graphs are passed as flat views of BaseGraph

@@ -217,7 +217,7 @@ def test_abi():
     new = ["cl_dotplot_params_default", "cl_kmer_dotplot_host", "cl_kmer_dotplot_compute", "cl_dotplot_tsv", "cl_dotplot_free"]
     for sym in new:
         assert sym in capi.EXPORTED_SYMBOLS and hasattr(lib, sym)
-    assert capi.ABI_VERSION == 21 == lib.cl_abi_version()
+    assert capi.ABI_VERSION == 22 == lib.cl_abi_version()
     assert C.sizeof(capi.DotplotEntry) == 16 == capi.DOTPLOT_ENTRY.itemsize
     # the header's layouts by hand (LP64): {int, u32, int, pad, double, u32, pad}, 4 x u32, {2 x u64, int, u32, u64, 2 pointers, u64, 2 pointers, 2 floats}
     assert [C.sizeof(capi.DotplotParams), C.sizeof(capi.DotplotEntry), C.sizeof(capi.DotplotC)] == [32, 16, 80]

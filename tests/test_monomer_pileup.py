@@ -420,7 +420,7 @@ def test_abi():
     for sym in new:
         assert sym in capi.EXPORTED_SYMBOLS and hasattr(lib, sym)
     lib.cl_abi_version.restype = C.c_int
-    assert lib.cl_abi_version() == 21
+    assert lib.cl_abi_version() == 22
     # the header's layouts by hand (LP64): {u64, 8 pointers, 2 floats}, {3 x u64, 4 floats}, {u64, 4 pointers, 2 x 4 bytes, pointer}
     sizes_by_hand = [80, 40, 56]
     assert [C.sizeof(capi.MonomerPileupC), C.sizeof(capi.MonomerRound), C.sizeof(capi.MonomerTemplatesC)] == sizes_by_hand

@@ -397,7 +397,7 @@ def test_abi():
     for sym in new:
         assert sym in capi.EXPORTED_SYMBOLS and hasattr(lib, sym)
     lib.cl_abi_version.restype = C.c_int
-    assert lib.cl_abi_version() == 21
+    assert lib.cl_abi_version() == 22
     assert C.sizeof(capi.MonomerBlock) == 24 == capi.MONOMER_BLOCK.itemsize
     # the header's layouts by hand (LP64): 7 x 4 bytes, 6 x 4 bytes, {3 x u64, 2 pointers, 2 floats}
     assert [C.sizeof(capi.MonomersParams), C.sizeof(capi.MonomerBlock), C.sizeof(capi.MonomerDecompositionC)] == [28, 24, 48]
