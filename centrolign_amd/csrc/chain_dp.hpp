@@ -306,10 +306,8 @@ struct ChainSwitches {
     bool walk2_debug;              // CL_CHAIN_WALK2_DEBUG: in-kernel counters and clocks of the walk (status[8..]), printed with CL_CHAIN_TIMING
     bool no_far;                   // CL_CHAIN_NO_FAR_PRUNE
     uint32_t far_lag;              // CL_CHAIN_FAR_LAG=1..kFarLag far launches in flight (0: the default)
-    int far_band;                  // CL_CHAIN_FAR_BAND=4..24 shift bucket width (default kFarBandShift)
     uint64_t far_arena_skip;       // CL_CHAIN_FAR_ARENA_SKIP=<words> left unused in front of the arena (tests: positions beyond 2^32 words on a small DP)
     bool seal_wave;                // CL_CHAIN_SEAL_WAVE: every node sealed by one wave (rounds 2-3, A/B)
-    uint32_t far_group, far_streams;   // CL_CHAIN_FAR_GROUP, CL_CHAIN_FAR_STREAMS (per-block path)
     const char* far_mode;          // CL_CHAIN_FAR_MODE: "sweep" / "bb" pin the far pass (A/B)
     bool ext_events;               // CL_CHAIN_EXT_EVENTS=0: hipEventRecord as in rounds 2-3 (A/B)
     bool far_early;                // CL_CHAIN_FAR_WAIT_LATE=1 clears it: far(k) issued as in round 4 (A/B)
@@ -329,7 +327,7 @@ struct ChainPath {
     uint32_t walk2_qpt = 1, walk2_help = 0;
     bool walk_reduce = false, group_path = false, packed = false;
     bool use_far = false;
-    uint32_t far_lag = 2, far_group = 1, far_streams = 1;
+    uint32_t far_lag = 2;
     const char* far_ran = "none";
     bool lazy_acc = false;
 };
@@ -465,7 +463,7 @@ struct ChainDev {
     int create_events(const ChainProblem& P);
     hipError_t enqueue(const ChainProblem& P, ChainPath& path, UnitsHeld& units);
     hipError_t enqueue_walk(const ChainProblem& P, ChainPath& path, hipError_t he);
-    hipError_t enqueue_blocks(const ChainProblem& P, const ChainPath& path, hipError_t he);
+    hipError_t enqueue_blocks(const ChainProblem& P, hipError_t he);
     void print_path(const ChainProblem& P, const ChainPath& path);
     int wait(const ChainProblem& P, const ChainPath& path, UnitsHeld& units, hipError_t he);
     int download(const ChainProblem& P, const ChainPath& path);

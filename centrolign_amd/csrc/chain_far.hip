@@ -761,9 +761,8 @@ hipError_t cl_chain_far_launch(const ClChainDevice& D, const ClFarDevice& F, uin
     ClFarDevice Fx = F;
     // workgroup w of a 1-D grid goes to XCD w % 8: with eight and more combinations every full round of eight is pinned, combination c to XCD c % 8, so that an
     // XCD's L2 holds the search structures of an eighth of the combinations (10 x 1 Mbp root, 25 combinations: HBM fetches per far launch 1 / 3, device time of the
-    // merge's DPs 874 -> 835 ms).  CL_CHAIN_FAR_XCD=0: the 2-D grid of rounds 2-4 (A/B)
-    static const bool xcd_env = [] { const char* e = getenv("CL_CHAIN_FAR_XCD"); return !e || e[0] != '0'; }();
-    if (xcd_env && mine >= 8) {
+    // merge's DPs 874 -> 835 ms); fewer combinations keep the 2-D grid of rounds 2-4
+    if (mine >= 8) {
         Fx.xcd_x = grid.x; Fx.xcd_n = mine;
         grid = dim3(mine * grid.x, 1);
     } else { Fx.xcd_x = 0; Fx.xcd_n = 0; }

@@ -290,12 +290,7 @@ cl_context* cl_context_create(int device_ordinal) {
     const int n_own = [] { const char* e = getenv("CL_CTX_STREAMS"); int v = e ? atoi(e) : 0; return v >= 1 && v <= kNumAuxStreams ? v : 6; }();
     ctx->n_aux = n_own;
     for (int i = 0; ok && i < kNumAuxStreams; ++i) {
-        // CL_CTX_PRIO_STREAMS=k: the first k auxiliary streams get the device's highest priority — a stitch plan deals its longest launches to them first
-        // (measurement knob, read at every creation like CL_CTX_STREAMS)
-        const int n_prio = [] { const char* e = getenv("CL_CTX_PRIO_STREAMS"); int v = e ? atoi(e) : 0; return v >= 0 && v <= kNumAuxStreams ? v : 0; }();
-        int prio_lo = 0, prio_hi = 0;
-        if (n_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        if (i < n_own) ok = (i < n_prio ? hipStreamCreateWithPriority(&ctx->aux[i], hipStreamNonBlocking, prio_hi) : hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking)) == hipSuccess;
+        if (i < n_own) ok = hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking) == hipSuccess;
         else ctx->aux[i] = ctx->aux[i % n_own];
         ok = ok && hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming) == hipSuccess;
     }

@@ -14,8 +14,7 @@ const ChainSwitches& chain_switches() {
     static const ChainSwitches sw = [] {
         const char *par_min = getenv("CL_CHAIN_PAR_RECORDS_MIN"), *fold = getenv("CL_CHAIN_WALK_FOLD"), *group = getenv("CL_CHAIN_GROUP_PATH"), *walk2 = getenv("CL_CHAIN_WALK2"),
                    *qpt = getenv("CL_CHAIN_WALK2_QPT"), *w2max = getenv("CL_CHAIN_WALK2_MAX"), *helpers = getenv("CL_CHAIN_WALK2_HELPERS"), *lag = getenv("CL_CHAIN_FAR_LAG"),
-                   *band = getenv("CL_CHAIN_FAR_BAND"), *skip = getenv("CL_CHAIN_FAR_ARENA_SKIP"), *fgroup = getenv("CL_CHAIN_FAR_GROUP"), *fstreams = getenv("CL_CHAIN_FAR_STREAMS"),
-                   *ext = getenv("CL_CHAIN_EXT_EVENTS"), *split = getenv("CL_CHAIN_NEAR_SPLIT");
+                   *skip = getenv("CL_CHAIN_FAR_ARENA_SKIP"), *ext = getenv("CL_CHAIN_EXT_EVENTS"), *split = getenv("CL_CHAIN_NEAR_SPLIT");
         ChainSwitches s{};
         s.par_records_min = par_min ? (uint64_t)atoll(par_min) : (uint64_t)(1u << 20);
         s.dense_queries = getenv("CL_CHAIN_DENSE_QUERIES") != nullptr;
@@ -31,11 +30,8 @@ const ChainSwitches& chain_switches() {
         s.walk2_debug = getenv("CL_CHAIN_WALK2_DEBUG") != nullptr;
         s.no_far = getenv("CL_CHAIN_NO_FAR_PRUNE") != nullptr;
         { const int v = lag ? atoi(lag) : 0; s.far_lag = (uint32_t)(v >= 1 && v <= (int)kFarLag ? v : 0); }
-        { const int v = band ? atoi(band) : 0; s.far_band = v >= 4 && v <= 24 ? v : kFarBandShift; }
         s.far_arena_skip = skip ? (uint64_t)strtoull(skip, nullptr, 10) & ~7ull : 0ull;
         s.seal_wave = getenv("CL_CHAIN_SEAL_WAVE") != nullptr;
-        s.far_group = fgroup ? std::max(1, atoi(fgroup)) : kChainFarGroup;
-        s.far_streams = fstreams ? std::min(4, std::max(1, atoi(fstreams))) : kChainFarStreams;
         s.far_mode = getenv("CL_CHAIN_FAR_MODE");
         s.ext_events = !ext || ext[0] != '0';
         s.far_early = getenv("CL_CHAIN_FAR_WAIT_LATE") == nullptr;
@@ -169,12 +165,9 @@ static ChainPath choose_path(const ChainProblem& P, bool allow_walk, PackLayout&
     path.use_far = path.use_walk && !sw.no_far && n_macro_all >= path.far_lag + 3;
     // Two streams.  The context's stream is the sequential one: per block b the one-workgroup walk of the block, preceded by
     // the "near" pass over the blocks the far launch could not see yet (folded into the walk kernel when there is a single
-    // combination).  The bulk is evaluated on an auxiliary stream ("far"): one launch serves a GROUP of kChainFarGroup
-    // consecutive blocks (a far launch lasts at least one tile, ~70 us, however few predecessors there are, and the far
-    // stream sets the pace: fewer, fatter launches) and reads the blocks before g0 - 1, final once walk(g0 - 2) is done.
-    path.far_group = sw.far_group;
-    // consecutive far launches alternate between auxiliary streams: while their grids are small their latency floors overlap
-    path.far_streams = sw.far_streams;
+    // combination).  The bulk is evaluated on an auxiliary stream ("far"): one launch per block (kChainFarGroup = 1), which
+    // reads the blocks before b - 1, final once walk(b - 2) is done.  Consecutive far launches alternate between
+    // kChainFarStreams auxiliary streams: while their grids are small their latency floors overlap
     // the stored query results of every combination (7 per pair): into the context's page-locked area when it can be had — 35 MB per
     // combination at 1.25 M pairs, 25 combinations at the root of a 10-sequence tree.  Beyond kLazyAccBytes (a root of 25 + 25 paths: 625
     // combinations, 21.9 GB at 1.25 M pairs — 4.3 s of copies into 22 GB of pageable memory, more than the DP itself) nothing is downloaded: the
@@ -457,9 +450,9 @@ int ChainDev::far_setup(const ChainProblem& P, ChainPath& path) {
         max_padded = std::max(max_padded, padded);
         r_pad += padded;
     }
-    // shift buckets: kFarBandShift wide (CL_CHAIN_FAR_BAND for measurements) unless bucket number and offset then do not fit the 32 bits of a
+    // shift buckets: kFarBandShift wide unless bucket number and offset then do not fit the 32 bits of a
     // bucket key: bucket << off_bits | offset, off_bits enough for the largest offset + 1 (what a query's offset bound can be)
-    uint32_t band_shift = (uint32_t)sw.far_band;
+    uint32_t band_shift = (uint32_t)kFarBandShift;
     uint32_t off_bits = 1;
     while (off_bits < 31 && ((uint64_t)max_off + 1) >> off_bits) ++off_bits;
     // buckets are numbered from 1; bucket + 2 must stay below 2^(32 - off_bits) - 1 (the query's upper neighbour bucket, and the padding key above all)
@@ -604,12 +597,12 @@ hipError_t ChainDev::enqueue(const ChainProblem& P, ChainPath& path, UnitsHeld& 
     if (walk_units && ctx->peers.n <= 1) { g_walk_units.take(ctx->device, units.n); units.held = true; }
     hipError_t he = hipEventRecord(ev0, ctx->stream);
     if (he == hipSuccess) he = hipEventRecord(ctx->ev_fork, ctx->stream);
-    for (uint32_t f = 0; f < path.far_streams && he == hipSuccess; ++f) he = hipStreamWaitEvent(ctx->aux[f], ctx->ev_fork, 0);
+    for (uint32_t f = 0; f < kChainFarStreams && he == hipSuccess; ++f) he = hipStreamWaitEvent(ctx->aux[f], ctx->ev_fork, 0);
     if (path.use_walk) he = enqueue_walk(P, path, he);
     else if (path.group_path) {
         for (size_t gi = 0; gi + 1 < group_first.size() && he == hipSuccess; ++gi)
             he = cl_chain_launch_group(D, group_first[gi], group_first[gi + 1], P.rec_off[group_first[gi + 1]] - P.rec_off[group_first[gi]], d_dp_enc.p, ctx->stream);
-    } else he = enqueue_blocks(P, path, he);
+    } else he = enqueue_blocks(P, he);
     if (he == hipSuccess) he = hipEventRecord(ev1, ctx->stream);
     return he;
 }
@@ -629,7 +622,7 @@ hipError_t ChainDev::enqueue_walk(const ChainProblem& P, ChainPath& path, hipErr
     hipStream_t seal_stream = ctx->aux[path.far_lag];   // right behind the far streams: the context's own streams are few (cl_context_create)
     if (path.use_far) {
         if (he == hipSuccess) he = hipStreamWaitEvent(seal_stream, ctx->ev_fork, 0);
-        for (uint32_t f = path.far_streams; f < path.far_lag && he == hipSuccess; ++f) he = hipStreamWaitEvent(ctx->aux[f], ctx->ev_fork, 0);
+        for (uint32_t f = kChainFarStreams; f < path.far_lag && he == hipSuccess; ++f) he = hipStreamWaitEvent(ctx->aux[f], ctx->ev_fork, 0);
     }
     // Branch-and-bound or sweep?  The far kernels count the leaves they had to open against the leaves in range (status[2..5]).
     // At a few checkpoints the host waits for the launches so far and reads the counts: once they cover enough queries with a
@@ -715,7 +708,7 @@ hipError_t ChainDev::enqueue_walk(const ChainProblem& P, ChainPath& path, hipErr
         const uint32_t b0 = k * bpm, near_lo = k >= lag ? (k - lag) * bpm : 0;
         bool far_recorded = false;
         if (near_lo > 0) {
-            hipStream_t far_stream = ctx->aux[k % (path.use_far ? path.far_lag : path.far_streams)];
+            hipStream_t far_stream = ctx->aux[k % (path.use_far ? path.far_lag : kChainFarStreams)];
             if (far_issued[k]) far_recorded = true;   // (sent at the end of iteration k - lag - 1)
             else if (path.use_far && far_bb && !shared) { he = issue_far_bb(k, false); far_recorded = true; }
             else if (path.use_far && far_bb) {
@@ -765,7 +758,7 @@ hipError_t ChainDev::enqueue_walk(const ChainProblem& P, ChainPath& path, hipErr
             ClChainDevice Dn = D;
             if (path.use_far && near_lo > 0) Dn.lo_mask = 63u;
             if (b_split > near_lo) {
-                hipStream_t near_stream = ctx->aux[(path.use_far ? path.far_lag : path.far_streams) + 1];
+                hipStream_t near_stream = ctx->aux[(path.use_far ? path.far_lag : kChainFarStreams) + 1];
                 he = hipStreamWaitEvent(near_stream, ev_walk[k - 2], 0);
                 if (he == hipSuccess) he = cl_chain_launch_inter(Dn, first, count, near_lo, b_split, P.max_recs(near_lo, b_split) + Dn.lo_mask, kChainNearTile, near_stream);
                 if (he == hipSuccess) he = cl_ring_event(ctx, 3, k, &ev_near_a);
@@ -806,29 +799,26 @@ hipError_t ChainDev::enqueue_walk(const ChainProblem& P, ChainPath& path, hipErr
     return he;
 }
 
-hipError_t ChainDev::enqueue_blocks(const ChainProblem& P, const ChainPath& path, hipError_t he) {
-    uint32_t near_lo = 0;   // first block the current group's far launch did not cover
+hipError_t ChainDev::enqueue_blocks(const ChainProblem& P, hipError_t he) {
+    static_assert(kChainFarGroup == 1, "a far launch per block");
     for (uint32_t b = 0; b < P.n_blocks && he == hipSuccess; ++b) {
         const uint32_t first = b * kChainBlock, count = (uint32_t)std::min<uint64_t>(kChainBlock, P.M - first);
-        if (b % path.far_group == 0) {
-            near_lo = b > 1 ? b - 1 : 0;
-            if (near_lo > 0) {
-                // far predecessors of the whole group: blocks [0, near_lo), final once walk(near_lo - 1) is done
-                hipStream_t far_stream = ctx->aux[(b / path.far_group) % path.far_streams];
-                he = hipStreamWaitEvent(far_stream, ev_intra[near_lo - 1], 0);
-                // a launch ends with one atomic merge per query and workgroup: small tiles (low latency) only where that is
-                // cheap — sparse mode has one maximum per query — and while the grid does not fill the chip
-                const uint32_t recs = P.max_recs(0, near_lo);
-                uint32_t tile = kChainFarTile;
-                if (P.sparse) {
-                    tile = kChainNearTile;
-                    while (tile < kChainFarTile && (recs + tile - 1) / tile > kChainFullGrid) tile *= 2;
-                }
-                const uint32_t group_count = (uint32_t)std::min<uint64_t>((uint64_t)path.far_group * kChainBlock, P.M - first);
-                if (he == hipSuccess) he = cl_chain_launch_inter(D, first, group_count, 0, near_lo, recs, tile, far_stream);
-                if (he == hipSuccess) he = hipEventCreateWithFlags(&ev_far[b], hipEventDisableTiming);
-                if (he == hipSuccess) he = hipEventRecord(ev_far[b], far_stream);
+        const uint32_t near_lo = b > 1 ? b - 1 : 0;   // first block the far launch does not cover
+        if (near_lo > 0) {
+            // far predecessors: blocks [0, near_lo), final once walk(near_lo - 1) is done
+            hipStream_t far_stream = ctx->aux[b % kChainFarStreams];
+            he = hipStreamWaitEvent(far_stream, ev_intra[near_lo - 1], 0);
+            // a launch ends with one atomic merge per query and workgroup: small tiles (low latency) only where that is
+            // cheap — sparse mode has one maximum per query — and while the grid does not fill the chip
+            const uint32_t recs = P.max_recs(0, near_lo);
+            uint32_t tile = kChainFarTile;
+            if (P.sparse) {
+                tile = kChainNearTile;
+                while (tile < kChainFarTile && (recs + tile - 1) / tile > kChainFullGrid) tile *= 2;
             }
+            if (he == hipSuccess) he = cl_chain_launch_inter(D, first, count, 0, near_lo, recs, tile, far_stream);
+            if (he == hipSuccess) he = hipEventCreateWithFlags(&ev_far[b], hipEventDisableTiming);
+            if (he == hipSuccess) he = hipEventRecord(ev_far[b], far_stream);
         }
         // near predecessors: blocks [near_lo, b), on the sequential stream right after walk(b - 1)
         const bool fuse_near = P.combos.size() == 1;
@@ -872,7 +862,7 @@ int ChainDev::wait(const ChainProblem& P, const ChainPath& path, UnitsHeld& unit
         (void)hipGetLastError();
     }
     if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-    for (uint32_t f = 0; f < std::max<uint32_t>(path.far_streams, path.far_lag) && he == hipSuccess; ++f) he = hipStreamSynchronize(ctx->aux[f]);
+    for (uint32_t f = 0; f < std::max<uint32_t>(kChainFarStreams, path.far_lag) && he == hipSuccess; ++f) he = hipStreamSynchronize(ctx->aux[f]);
     if (units.held) { g_walk_units.give(ctx->device, units.n); units.held = false; }   // (the device is done with this DP's launches)
     if (he != hipSuccess) return chain_hip_fail(ctx, he, "chaining DP kernels");
     if (path.use_walk) {

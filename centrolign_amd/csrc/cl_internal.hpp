@@ -233,9 +233,9 @@ void cl_set_error(cl_context* ctx, const char* fmt, ...);
         }                                                                                         \
     } while (0)
 
-// Blocking copy WITHOUT the legacy default stream: a hipMemcpy on the legacy stream fails ("operation would make the legacy
-// stream depend on a capturing blocking stream") while ANOTHER thread of the process captures its stitch plan into a hipGraph, so
-// every copy of this library goes through the context's own (non-blocking) stream and waits for it.
+// Blocking copy WITHOUT the legacy default stream: every copy of this library goes through the context's own (non-blocking) stream
+// and waits for it, so that it orders with nothing but that context's work (a hipMemcpy on the legacy stream also fails, "operation
+// would make the legacy stream depend on a capturing blocking stream", while ANOTHER thread of the process captures a stream).
 inline hipError_t cl_copy_sync(cl_context* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     if (bytes == 0) return hipSuccess;
     hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);

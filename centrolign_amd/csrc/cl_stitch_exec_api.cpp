@@ -1,4 +1,4 @@
-// cl_stitch_exec_api.cpp — a stitch plan's execution: its launches over the context's streams (launch_group, enqueue_groups, cl_stitch_join), the passes
+// cl_stitch_exec_api.cpp — a stitch plan's execution: its launches over the context's streams (launch_group, profile_groups, enqueue_groups, cl_stitch_join), the passes
 // (cl_stitch_plan_execute / _execute_profiled / _execute_evented / _sync), what a plan reports (_stats, _launch_info), the results (_collect), its release, and the
 // one-shot entry points that make, run and collect a plan per chunk of a batch (run_whole / run_chunk: cl_po_poa_batch, cl_stitch_batch_align).
 // The plan itself is made in cl_stitch_plan_api.cpp; stitch_plan.hpp is what the two share.
@@ -20,17 +20,48 @@
 
 namespace {
 
-// CL_STITCH_GRAPH=1 replays a captured hipGraph of a plan's launches instead of launching the kernels directly (rounds 1-3 did; measured in
-// round 4 on the 10 x 1 Mbp batches: one plan of 16 launches 4.24 ms per step through the graph, 3.12 ms launched directly — the graph's branches do
-// not start together); CL_NO_GRAPH=1 is the old name of "off"
-const bool g_no_graph = [] { const char* e = getenv("CL_STITCH_GRAPH"); return !(e && *e == '1'); }();
-
 int64_t pure_deletion_score(size_t path_len, int npw, const cl_align_params& p) {
     if (path_len == 0) return 0;
     // alignment.hpp:1202-1205 evaluates -open - extend in uint32_t before widening; reproduced literally
     int64_t s = std::numeric_limits<int64_t>::max();
     for (int k = 0; k < npw; ++k) s = std::min<int64_t>(s, (int64_t)(uint32_t)(0u - p.gap_open[k] - p.gap_extend[k]));
     return s;
+}
+
+// ---- cl_stitch_plan_collect's helpers ----
+// what the launches left per PO-POA problem, on the host
+struct PlanOutputs {
+    std::vector<uint32_t> len, status;
+    std::vector<int32_t> score;
+    std::vector<uint2> pairs;
+};
+int download_outputs(cl_context* ctx, const cl_stitch_plan* pl, PlanOutputs& o) {
+    const size_t npo = pl->desc.size();
+    o.len.resize(npo); o.status.resize(npo); o.score.resize(npo); o.pairs.resize(pl->d_out_pairs.n);
+    if (!npo) return CL_OK;
+    HIP_TRY(ctx, cl_copy_sync(ctx, o.len.data(), pl->d_out_len.p, npo * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, cl_copy_sync(ctx, o.status.data(), pl->d_out_status.p, npo * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, cl_copy_sync(ctx, o.score.data(), pl->d_out_score.p, npo * 4, hipMemcpyDeviceToHost));
+    if (!o.pairs.empty()) HIP_TRY(ctx, cl_copy_sync(ctx, o.pairs.data(), pl->d_out_pairs.p, o.pairs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    return CL_OK;
+}
+
+// Pairs that gave up waiting (status 9) run again on a kernel that waits for nobody — same planes, same output slots: the list is uploaded, launch(dev, list, count)
+// enqueued on the context's stream and waited for, the pairs counted as fallbacks.  `what`: the pairs and the kernel, for the error text
+template <class Launch>
+int rerun_pairs(cl_context* ctx, cl_stitch_plan* pl, const std::vector<uint32_t>& again, const char* what, Launch launch) {
+    DevBuf<uint32_t> d_again;
+    int rc = d_again.upload(ctx, again);
+    if (rc) return rc;
+    ClDeviceBatch dev = pl->dev;
+    dev.ticks = nullptr;
+    hipError_t e = launch(dev, d_again.p, (uint32_t)again.size());
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    d_again.release();
+    if (e != hipSuccess) { set_error(ctx, "re-running %zu %s failed: %s", again.size(), what, hipGetErrorString(e)); return CL_ERR_HIP; }
+    pl->stats.n_strip_fallbacks += again.size();
+    cl_fallbacks.strip_fallbacks += again.size();
+    return CL_OK;
 }
 
 }  // namespace
@@ -53,18 +84,12 @@ void cl_stitch_plan_free(cl_stitch_plan* pl) {
         if (g.ev0) (void)hipEventDestroy(g.ev0);
         if (g.ev1) (void)hipEventDestroy(g.ev1);
     }
-    if (pl->graph_exec) (void)hipGraphExecDestroy(pl->graph_exec);
-    if (pl->graph) (void)hipGraphDestroy(pl->graph);
     if (pl->ev_start) (void)hipEventDestroy(pl->ev_start);
     if (pl->ev_stop) (void)hipEventDestroy(pl->ev_stop);
     delete pl;
 }
 
 extern "C" {
-
-// auxiliary streams a plan spreads its launches over (CL_STITCH_STREAMS, 1..kNumAuxStreams): many contexts at once share the process's
-// hardware queues, and launches of different streams that land on one queue run one after the other
-static const int g_plan_streams = [] { const char* e = getenv("CL_STITCH_STREAMS"); int v = e ? atoi(e) : 0; return v >= 1 && v <= kNumAuxStreams ? v : kNumAuxStreams; }();
 
 // a launch group -> its launcher call: the one place that knows which launcher, with which arguments, a variant is
 static hipError_t launch_group(const LaunchGroup& g, cl_stitch_plan* pl, const ClDeviceBatch& dev, hipStream_t stream) {
@@ -128,42 +153,42 @@ static int plan_mark_stop(cl_context* ctx, cl_stitch_plan* pl) {
     return CL_OK;
 }
 
-// Enqueue every launch group of the plan as a fork/join over the auxiliary streams; `timed`: the profiled pass (every launch alone, timed by the host's
-// clock and the kernel's own).
-static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl, bool timed, bool join_now = false) {
-    if (timed) {
-        // the profiled pass: every launch ALONE on the context's stream, the device idle before and after, timed by the HOST's clock round
-        // launch + wait.  HIP event pairs read about twice the kernel's duration in the rocprofv3 kernel trace here (round 4: 2.87 ms by events,
-        // 1.43 ms in the trace for the dominant launch, also with nothing else on the device); the host's clock round launch + wait reads the
-        // kernel plus ~20 us of launch and wake-up latency, i.e. agrees with the trace within a few per cent for the launches that matter
-        // (a launch that finds the device idle runs at about half speed — the dominant launch 2.9 ms against 1.45 ms behind another launch, with the
-        // shader clock already at its top in both cases: whatever ramps, ramps within the first launch — so the duration reported is that of a launch
-        // behind another one, which is what a launch inside a step is, and what the rocprofv3 kernel trace of a step shows)
-        { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
+// The profiled pass: every launch ALONE on the context's stream, the device idle before and after, timed by the HOST's clock round
+// launch + wait and by the kernel's own.  HIP event pairs read about twice the kernel's duration in the rocprofv3 kernel trace here (round 4: 2.87 ms by events,
+// 1.43 ms in the trace for the dominant launch, also with nothing else on the device); the host's clock round launch + wait reads the
+// kernel plus ~20 us of launch and wake-up latency, i.e. agrees with the trace within a few per cent for the launches that matter
+// (a launch that finds the device idle runs at about half speed — the dominant launch 2.9 ms against 1.45 ms behind another launch, with the
+// shader clock already at its top in both cases: whatever ramps, ramps within the first launch — so the duration reported is that of a launch
+// behind another one, which is what a launch inside a step is, and what the rocprofv3 kernel trace of a step shows)
+static int profile_groups(cl_context* ctx, cl_stitch_plan* pl) {
+    { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t ng = pl->groups.size();
+    if (!pl->d_ticks.p) { int rc = pl->d_ticks.alloc(ctx, 2 * ng); if (rc) return rc; }
+    for (size_t gi = 0; gi < ng; ++gi) {
+        LaunchGroup& g = pl->groups[gi];
+        // the kernel's own clock: first workgroup's start, last workgroup's end (s_memrealtime, 100 MHz) — what the rocprofv3 kernel trace shows;
+        // beside it the host's clock round launch + wait
+        ClDeviceBatch dev = pl->dev;
+        dev.ticks = pl->d_ticks.p + 2 * gi;
+        dev.tick_pass = 0xFFFFu;
+        HIP_TRY(ctx, launch_group(g, pl, dev, ctx->stream));   // (first run: whatever ramps with the device idle, ramps here)
+        HIP_TRY(ctx, hipMemsetAsync(dev.ticks, 0, 2 * sizeof(unsigned long long), ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t ng = pl->groups.size();
-        if (!pl->d_ticks.p) { int rc = pl->d_ticks.alloc(ctx, 2 * ng); if (rc) return rc; }
-        for (size_t gi = 0; gi < ng; ++gi) {
-            LaunchGroup& g = pl->groups[gi];
-            // the kernel's own clock: first workgroup's start, last workgroup's end (s_memrealtime, 100 MHz) — what the rocprofv3 kernel trace shows;
-            // beside it the host's clock round launch + wait
-            ClDeviceBatch dev = pl->dev;
-            dev.ticks = pl->d_ticks.p + 2 * gi;
-            dev.tick_pass = 0xFFFFu;
-            HIP_TRY(ctx, launch_group(g, pl, dev, ctx->stream));   // (first run: whatever ramps with the device idle, ramps here)
-            HIP_TRY(ctx, hipMemsetAsync(dev.ticks, 0, 2 * sizeof(unsigned long long), ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            const auto t0 = std::chrono::steady_clock::now();
-            HIP_TRY(ctx, launch_group(g, pl, dev, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            g.host_idle_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            unsigned long long got[2] = {0, 0};
-            HIP_TRY(ctx, cl_copy_sync(ctx, got, dev.ticks, sizeof(got), hipMemcpyDeviceToHost));
-            const double us = tick_span_us(got[0], got[1]);
-            g.host_ms = us > 0 ? (float)(us * 1e-3) : g.host_idle_ms;
-        }
-        return CL_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_TRY(ctx, launch_group(g, pl, dev, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        g.host_idle_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        unsigned long long got[2] = {0, 0};
+        HIP_TRY(ctx, cl_copy_sync(ctx, got, dev.ticks, sizeof(got), hipMemcpyDeviceToHost));
+        const double us = tick_span_us(got[0], got[1]);
+        g.host_ms = us > 0 ? (float)(us * 1e-3) : g.host_idle_ms;
     }
+    return CL_OK;
+}
+
+// The concurrent pass: every launch group of the plan enqueued as a fork/join over the context's auxiliary streams.
+static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl) {
     // every launch also leaves its own clock's start / end (two atomics per workgroup): cl_stitch_plan_launch_info reports the durations of the LAST pass,
     // i.e. of launches that overlap with one another as they do in production
     // (the words are not zeroed between passes: a pass's number in their top bits makes its clocks win over every earlier pass's; zeroed when the number wraps and
@@ -190,23 +215,19 @@ static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl, bool timed, bool 
     bool used[kNumAuxStreams] = {};
     // the groups come longest first (cl_stitch_plan_create: estimated duration = longest sweep x the kernel's time per step); each goes to the
     // stream with the least work so far (longest-processing-time rule), so that the one or two long sweeps of a batch start at once on streams
-    // of their own and the short launches queue up beside, not behind, them.  CL_STITCH_SCHED=rr deals them round-robin (rounds 1-3; A/B).
-    static const bool round_robin = [] { const char* e = getenv("CL_STITCH_SCHED"); return e && e[0] == 'r'; }();
-    const int n_streams = std::min(g_plan_streams, ctx->n_aux);
+    // of their own and the short launches queue up beside, not behind, them.
+    const int n_streams = ctx->n_aux;
     uint64_t load[kNumAuxStreams] = {};
     std::vector<int> stream_of(pl->groups.size());
     for (size_t gi = 0; gi < pl->groups.size(); ++gi) {
-        int si = (int)(gi % (size_t)n_streams);
-        if (!round_robin) {
-            si = 0;
-            for (int t = 1; t < n_streams; ++t) if (load[t] < load[si]) si = t;
-            load[si] += std::max<uint64_t>(1, pl->groups[gi].est_cost);
-        }
+        int si = 0;
+        for (int t = 1; t < n_streams; ++t) if (load[t] < load[si]) si = t;
+        load[si] += std::max<uint64_t>(1, pl->groups[gi].est_cost);
         stream_of[gi] = si;
     }
     static const bool sched_log = getenv("CL_STITCH_SCHED_LOG") != nullptr;   // the deal, once per change of the groups' order: stream, estimated duration, workgroups, kind
     if (sched_log && pl->tick_pass <= 1) {
-        fprintf(stderr, "[stitch plan] launches over %d streams (calibrated %d, re-dealings left %d):", n_streams, (int)pl->calibrated, pl->recalibrations_left);
+        fprintf(stderr, "[stitch plan] launches over %d streams (calibrated %d, re-dealings left %d):", n_streams, (int)pl->calibrated, pl->redeals_left);
         for (int t = 0; t < n_streams; ++t) {
             fprintf(stderr, "  s%d %llu us [", t, (unsigned long long)load[t]);
             for (size_t gi = 0; gi < pl->groups.size(); ++gi)
@@ -219,12 +240,11 @@ static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl, bool timed, bool 
     // the last of them has a compute unit — for the 34 716 workgroups of the short chain pairs that is the launch's whole duration), and in the step of 10 x 1 Mbp the
     // launch that ends the step — 66 long near-chain pairs, 1.27 ms — was started 0.43 ms after the first one (scripts/dev/step_timeline.py).  Launches of few workgroups
     // (at most two per compute unit: resident at once, their queue is free again at once) therefore go first, the wide ones after them; each on the stream the
-    // longest-processing-time rule gave it.  CL_STITCH_ORDER=cost: in the order of their durations (up to the first half of round 5)
-    static const bool light_first = [] { const char* e = getenv("CL_STITCH_ORDER"); return !(e && e[0] == 'c'); }();
+    // longest-processing-time rule gave it.
     for (int pass = 0; pass < 2; ++pass)
         for (size_t gi = 0; gi < pl->groups.size(); ++gi) {
             const LaunchGroup& g = pl->groups[gi];
-            const bool light = light_first && g.count <= 512;
+            const bool light = g.count <= 512;
             if (light != (pass == 0)) continue;
             const int si = stream_of[gi];
             if (!used[si]) { HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux[si], ctx->ev_fork, 0)); used[si] = true; }
@@ -246,7 +266,44 @@ static int enqueue_groups(cl_context* ctx, cl_stitch_plan* pl, bool timed, bool 
             ctx->stitch_join_pending |= 1u << si;
         }
     pl->stop_pending = true;
-    if (eager_join || join_now) return plan_mark_stop(ctx, pl);
+    return eager_join ? plan_mark_stop(ctx, pl) : CL_OK;   // (otherwise the end of the pass is marked when somebody joins: plan_mark_stop)
+}
+
+// The launches longest first again, by the est_cost a re-deal has just given them.  The tick words belong to the launches in their OLD order: the next pass starts them afresh.
+static void sort_groups_by_cost(cl_stitch_plan* pl) {
+    std::stable_sort(pl->groups.begin(), pl->groups.end(), [](const LaunchGroup& x, const LaunchGroup& y) { return x.est_cost > y.est_cost; });
+    pl->tick_pass = 0;
+}
+
+// First re-deal, by the durations measured ALONE: a plan that is executed again (resident inputs, replayed passes) measures its launches ONCE — each alone on the
+// device, the host's clock round launch + wait — and deals them over the streams by those durations from then on: a launch lasts as long as its longest sweep at a
+// rate that depends on the subproblems' branching (0.25 .. 2.7 us per step), which the estimate of cl_stitch_plan_create cannot know.
+// Measured on the 10 x 1 Mbp batches as one plan: 3.03 ms per step with the estimate (the stream that got 1.40 + 0.70 + 0.79 ms sets the
+// pace), the sum of the sixteen launches is 12.8 ms over six streams.
+static int redeal_by_solo_durations(cl_context* ctx, cl_stitch_plan* pl) {
+    int rc = profile_groups(ctx, pl);
+    if (rc) return rc;
+    for (LaunchGroup& g : pl->groups) g.est_cost = (uint64_t)(g.host_ms * 1000.f) + 1;
+    sort_groups_by_cost(pl);
+    return CL_OK;
+}
+
+// Second re-deal, by the launches' OWN clocks inside the previous pass: a launch alone and the same launch among fifteen others are different things — in the timed
+// step of 10 x 1 Mbp the chain kernel's launch of 221 long pairs takes 0.4 ms alone and 1.7 ms in the step (its sixteen waves per workgroup wait for SIMDs they share),
+// so the first re-deal put a 0.28 ms launch behind it on its stream, and that stream ended the step 0.2 ms after every other one (scripts/dev/step_timeline.py).  So
+// the pass after the first concurrent one deals the launches out again by the durations their own clocks showed (first workgroup's start to last workgroup's end,
+// queueing for compute units included — which is what a stream is busy for).  One wait for the stream + one small copy, once per plan: its third pass, which is
+// still a warm-up pass of bench.py.  The deal stays as it is where a launch's clocks are not of one pass.
+static int redeal_by_in_pass_clocks(cl_context* ctx, cl_stitch_plan* pl) {
+    { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t ng = pl->groups.size();
+    std::vector<unsigned long long> got(2 * ng);
+    HIP_TRY(ctx, cl_copy_sync(ctx, got.data(), pl->d_ticks.p, got.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t gi = 0; gi < ng; ++gi)
+        if (!(tick_span_us(got[2 * gi], got[2 * gi + 1]) > 0)) return CL_OK;
+    for (size_t gi = 0; gi < ng; ++gi) pl->groups[gi].est_cost = (uint64_t)tick_span_us(got[2 * gi], got[2 * gi + 1]) + 1;
+    sort_groups_by_cost(pl);
     return CL_OK;
 }
 
@@ -254,86 +311,22 @@ int cl_stitch_plan_execute(cl_context* ctx, cl_stitch_plan* pl) {
     if (!ctx || !pl) { set_error(ctx, "null argument"); return CL_ERR_INVALID_ARGUMENT; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ++cl_fallbacks.stitch_plans;
-    // A plan that is executed again (resident inputs, replayed passes) measures its launches ONCE — each alone on the device, the host's clock
-    // round launch + wait — and deals them over the streams by those durations from then on: a launch lasts as long as its longest sweep at a
-    // rate that depends on the subproblems' branching (0.25 .. 2.7 us per step), which the estimate of cl_stitch_plan_create cannot know.
-    // Measured on the 10 x 1 Mbp batches as one plan: 3.03 ms per step with the estimate (the stream that got 1.40 + 0.70 + 0.79 ms sets the
-    // pace), the sum of the sixteen launches is 12.8 ms over six streams.  CL_STITCH_CALIBRATE=0: the estimate only
-    static const bool calibrate = [] { const char* e = getenv("CL_STITCH_CALIBRATE"); return !e || e[0] != '0'; }();
-    if (calibrate && pl->executed && !pl->calibrated && pl->groups.size() > 2) {
-        pl->calibrated = true;
-        int rc = enqueue_groups(ctx, pl, true);
+    // a plan of more than two launches is dealt over the streams again in front of its second pass and, once, in front of the pass after that
+    if (pl->groups.size() > 2) {
+        int rc = CL_OK;
+        if (pl->executed && !pl->calibrated) {
+            pl->calibrated = true;
+            rc = redeal_by_solo_durations(ctx, pl);
+        } else if (pl->calibrated && pl->redeals_left > 0 && pl->d_ticks.p) {
+            --pl->redeals_left;
+            rc = redeal_by_in_pass_clocks(ctx, pl);
+        }
         if (rc) return rc;
-        for (LaunchGroup& g : pl->groups) g.est_cost = (uint64_t)(g.host_ms * 1000.f) + 1;
-        std::stable_sort(pl->groups.begin(), pl->groups.end(), [](const LaunchGroup& x, const LaunchGroup& y) { return x.est_cost > y.est_cost; });
-        pl->tick_pass = 0;
-    }
-    // Second stage: a launch alone and the same launch among fifteen others are different things — in the timed step of 10 x 1 Mbp the chain kernel's launch of 221 long
-    // pairs takes 0.4 ms alone and 1.7 ms in the step (its sixteen waves per workgroup wait for SIMDs they share), so the first stage put a 0.28 ms launch behind it on
-    // its stream, and that stream ended the step 0.2 ms after every other one (scripts/dev/step_timeline.py).  So the pass after the first concurrent one deals
-    // the launches out again by the durations their OWN clocks showed inside the previous pass (first workgroup's start to last workgroup's end, queueing for
-    // compute units included — which is what a stream is busy for).  One wait for the stream + one small copy + one more graph capture, once per plan.  CL_STITCH_CALIBRATE=1: first stage only
-    static const bool second_stage = [] { const char* e = getenv("CL_STITCH_CALIBRATE"); return !e || e[0] == '2'; }();
-    // (how often: once — the third pass of a plan, which is still a warm-up pass of bench.py; CL_STITCH_RECAL=0..3 for measurements)
-    static const int recal_env = [] { const char* e = getenv("CL_STITCH_RECAL"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : v > 3 ? 3 : v; }();
-    if (pl->recalibrations_left < 0) pl->recalibrations_left = recal_env;
-    if (calibrate && second_stage && pl->calibrated && pl->concurrent_passes >= 1 && pl->recalibrations_left > 0 && pl->groups.size() > 2 && pl->d_ticks.p) {
-        --pl->recalibrations_left;
-        pl->concurrent_passes = 0;
-        { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<unsigned long long> got(2 * pl->groups.size());
-        HIP_TRY(ctx, cl_copy_sync(ctx, got.data(), pl->d_ticks.p, got.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        bool all = true;
-        for (size_t gi = 0; gi < pl->groups.size(); ++gi) all = all && tick_span_us(got[2 * gi], got[2 * gi + 1]) > 0;
-        if (all) {
-            for (size_t gi = 0; gi < pl->groups.size(); ++gi) pl->groups[gi].est_cost = (uint64_t)tick_span_us(got[2 * gi], got[2 * gi + 1]) + 1;
-            pl->tick_pass = 0;   // (the words belong to the launches in their OLD order: start afresh)
-            std::stable_sort(pl->groups.begin(), pl->groups.end(), [](const LaunchGroup& x, const LaunchGroup& y) { return x.est_cost > y.est_cost; });
-            if (pl->graph_exec) { (void)hipGraphExecDestroy(pl->graph_exec); pl->graph_exec = nullptr; }
-            if (pl->graph) { (void)hipGraphDestroy(pl->graph); pl->graph = nullptr; }
-            pl->graph_tried = false;
-        }
-    }
-    // The launch DAG (one kernel per group, all independent) is captured once into a hipGraph and replayed:
-    // a dozen kernels start together instead of trickling out at the host's enqueue rate.
-    if (!pl->graph_tried && !g_no_graph && !pl->groups.empty()) {
-        pl->graph_tried = true;
-        hipGraph_t graph = nullptr;
-        // (nothing uncaptured may be waited for inside a capture: join what is out first; and the launch clocks are zeroed by a node of the graph — a replayed
-        // pass carries the same pass number every time)
-        { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
-        pl->tick_pass = 0;
-        if (!pl->d_ticks.p) { int rc = pl->d_ticks.alloc(ctx, 2 * pl->groups.size()); if (rc) return rc; }   // (no allocation inside a capture)
-        if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            int rc = enqueue_groups(ctx, pl, false, true);   // (a capture has to end with every forked stream joined)
-            hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
-            if (rc == CL_OK && e == hipSuccess && graph &&
-                hipGraphInstantiate(&pl->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                pl->graph = graph;
-            } else {
-                if (graph) (void)hipGraphDestroy(graph);
-                pl->graph_exec = nullptr;
-                (void)hipGetLastError();
-            }
-        } else {
-            (void)hipGetLastError();
-        }
     }
     HIP_TRY(ctx, hipEventRecord(pl->ev_start, ctx->stream));
-    if (pl->graph_exec) {
-        // (a pass enqueued without the graph — the evented pass, a pass before the capture — may still be running on the auxiliary streams: the graph's launches use
-        // the same queue words and progress words, so it waits for them)
-        { int rc = cl_stitch_join(ctx); if (rc) return rc; }
-        HIP_TRY(ctx, hipGraphLaunch(pl->graph_exec, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(pl->ev_stop, ctx->stream));
-        pl->stop_pending = false;
-    } else {
-        int rc = enqueue_groups(ctx, pl, false);   // (the end of the pass is marked when somebody joins: plan_mark_stop)
-        if (rc) return rc;
-    }
+    int rc = enqueue_groups(ctx, pl);
+    if (rc) return rc;
     pl->executed = true;
-    if (pl->calibrated) ++pl->concurrent_passes;
     return CL_OK;
 }
 
@@ -342,7 +335,7 @@ int cl_stitch_plan_execute_profiled(cl_context* ctx, cl_stitch_plan* pl) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
     HIP_TRY(ctx, hipEventRecord(pl->ev_start, ctx->stream));
-    int rc = enqueue_groups(ctx, pl, true);
+    int rc = profile_groups(ctx, pl);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(pl->ev_stop, ctx->stream));
     pl->executed = true;
@@ -351,7 +344,7 @@ int cl_stitch_plan_execute_profiled(cl_context* ctx, cl_stitch_plan* pl) {
     return CL_OK;
 }
 
-// A concurrent pass exactly as cl_stitch_plan_execute enqueues one without a graph — the same launches on the same streams, side by side, following the pass before in
+// A concurrent pass exactly as cl_stitch_plan_execute enqueues one — the same launches on the same streams, side by side, following the pass before in
 // stream order — with a pair of HIP events round every launch ON ITS STREAM.  An event pair spans from the moment the stream reaches the launch (the end of whatever
 // preceded it there) to the launch's completion, end-of-kernel cache write-back included: what the rocprofv3 kernel trace of a step shows as the dispatch's duration plus
 // the stream's launch gap, i.e. an UPPER bound of the trace's duration where the kernel's own clock (first workgroup's start to last workgroup's end) is a lower bound.
@@ -361,7 +354,7 @@ int cl_stitch_plan_execute_evented(cl_context* ctx, cl_stitch_plan* pl) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventRecord(pl->ev_start, ctx->stream));
     pl->event_pass = true;
-    const int rc = enqueue_groups(ctx, pl, false);
+    const int rc = enqueue_groups(ctx, pl);
     pl->event_pass = false;
     if (rc) return rc;
     pl->executed = true;
@@ -458,72 +451,43 @@ int cl_stitch_plan_collect(cl_context* ctx, cl_stitch_plan* pl, cl_stitch_result
     { int rc = plan_mark_stop(ctx, pl); if (rc) return rc; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npo = pl->desc.size();
-    std::vector<uint32_t> len(npo), status(npo);
-    std::vector<int32_t> score(npo);
-    std::vector<uint2> pairs(pl->d_out_pairs.n);
-    if (npo) {
-        HIP_TRY(ctx, cl_copy_sync(ctx, len.data(), pl->d_out_len.p, npo * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, cl_copy_sync(ctx, status.data(), pl->d_out_status.p, npo * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, cl_copy_sync(ctx, score.data(), pl->d_out_score.p, npo * 4, hipMemcpyDeviceToHost));
-        if (!pairs.empty()) HIP_TRY(ctx, cl_copy_sync(ctx, pairs.data(), pl->d_out_pairs.p, pairs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
-    }
-    // a pair whose strips gave up waiting for one another (status 9: popoa_strip_kernel's waits are bounded, and the strips of a launch can be kept apart
-    // by whatever else crowds the device) is run again by the anti-diagonal kernel, which waits for nobody — same planes, same output slots
+    PlanOutputs got;
+    { int rc = download_outputs(ctx, pl, got); if (rc) return rc; }
     {
-        std::vector<uint32_t> redo[4];
-        for (size_t i = 0; i < npo; ++i)
-            if (status[i] == 9 && (pl->desc[i].kind == CL_KIND_STRIP || pl->desc[i].kind == CL_KIND_LANE)) redo[pl->desc[i].npw].push_back((uint32_t)i);
+        // a chain pair whose groups gave up waiting for one another (popoa_linear_span_kernel) is run again by the one-workgroup chain kernel: same codes, same hand-off rows
+        std::vector<uint32_t> chain_again, redo[4];
+        // ... and a pair whose strips did (popoa_strip_kernel's waits are bounded, and the strips of a launch can be kept apart by whatever else crowds the device)
+        // by the anti-diagonal kernel
+        for (size_t i = 0; i < npo; ++i) {
+            if (got.status[i] != 9) continue;
+            if (pl->desc[i].kind == CL_KIND_LINEAR) chain_again.push_back((uint32_t)i);
+            else if (pl->desc[i].kind == CL_KIND_STRIP || pl->desc[i].kind == CL_KIND_LANE) redo[pl->desc[i].npw].push_back((uint32_t)i);
+        }
         bool any = false;
-        {   // ... and a chain pair whose groups gave up waiting for one another (popoa_linear_span_kernel) by the one-workgroup chain kernel: same codes, same hand-off rows
-            std::vector<uint32_t> again;
-            for (size_t i = 0; i < npo; ++i)
-                if (status[i] == 9 && pl->desc[i].kind == CL_KIND_LINEAR) again.push_back((uint32_t)i);
-            if (!again.empty()) {
-                any = true;
-                DevBuf<uint32_t> d_again;
-                int rc = d_again.upload(ctx, again);
-                if (rc) return rc;
-                ClDeviceBatch dev = pl->dev;
-                dev.ticks = nullptr;
-                hipError_t e = cl_launch_popoa_linear(16, (uint32_t)again.size(), dev, d_again.p, pl->sparams, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                d_again.release();
-                if (e != hipSuccess) { set_error(ctx, "re-running %zu chain pairs on one workgroup each failed: %s", again.size(), hipGetErrorString(e)); return CL_ERR_HIP; }
-                pl->stats.n_strip_fallbacks += again.size();
-                cl_fallbacks.strip_fallbacks += again.size();
-            }
+        if (!chain_again.empty()) {
+            any = true;
+            int rc = rerun_pairs(ctx, pl, chain_again, "chain pairs on one workgroup each", [&](const ClDeviceBatch& dev, const uint32_t* list, uint32_t count) {
+                return cl_launch_popoa_linear(16, count, dev, list, pl->sparams, ctx->stream); });
+            if (rc) return rc;
         }
         for (int npw = 1; npw <= 3; ++npw) {
             if (redo[npw].empty()) continue;
             any = true;
-            DevBuf<uint32_t> d_redo;
-            int rc = d_redo.upload(ctx, redo[npw]);
+            int rc = rerun_pairs(ctx, pl, redo[npw], "pairs on the anti-diagonal kernel", [&](const ClDeviceBatch& dev, const uint32_t* list, uint32_t count) {
+                return cl_launch_popoa_general(npw, 1024, count, 0, dev, list, pl->sparams, ctx->stream); });
             if (rc) return rc;
-            ClDeviceBatch dev = pl->dev;
-            dev.ticks = nullptr;
-            hipError_t e = cl_launch_popoa_general(npw, 1024, (uint32_t)redo[npw].size(), 0, dev, d_redo.p, pl->sparams, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            d_redo.release();
-            if (e != hipSuccess) { set_error(ctx, "re-running %zu pairs on the anti-diagonal kernel failed: %s", redo[npw].size(), hipGetErrorString(e)); return CL_ERR_HIP; }
-            pl->stats.n_strip_fallbacks += redo[npw].size();
-            cl_fallbacks.strip_fallbacks += redo[npw].size();
         }
-        if (any) {
-            HIP_TRY(ctx, cl_copy_sync(ctx, len.data(), pl->d_out_len.p, npo * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, cl_copy_sync(ctx, status.data(), pl->d_out_status.p, npo * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, cl_copy_sync(ctx, score.data(), pl->d_out_score.p, npo * 4, hipMemcpyDeviceToHost));
-            if (!pairs.empty()) HIP_TRY(ctx, cl_copy_sync(ctx, pairs.data(), pl->d_out_pairs.p, pairs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
-        }
+        if (any) { int rc = download_outputs(ctx, pl, got); if (rc) return rc; }
     }
     const uint64_t n = pl->n_problems;
     uint64_t total = 0;
     for (size_t i = 0; i < npo; ++i) {
-        if (status[i] != 0) {
+        if (got.status[i] != 0) {
             set_error(ctx, "device traceback failed on problem %llu (status %u): no source..sink connection or corrupt input",
-                      (unsigned long long)pl->po_problem[i], status[i]);
+                      (unsigned long long)pl->po_problem[i], got.status[i]);
             return CL_ERR_UNREACHABLE_SINK;
         }
-        total += len[i];
+        total += got.len[i];
     }
     for (uint32_t k : pl->pd_problem) total += pl->pd_path[k].size();
     for (uint32_t k : pl->host_problem) total += pl->host_aln[k].size();
@@ -546,10 +510,11 @@ int cl_stitch_plan_collect(cl_context* ctx, cl_stitch_plan* pl, cl_stitch_result
             const size_t i = (size_t)pl->po_index[k];
             const ClProbDesc& d = pl->desc[i];
             const uint32_t cap = d.n1 + d.n2;
-            const uint2* src = pairs.data() + d.out_base + (cap - len[i]);
+            const uint32_t len = got.len[i];
+            const uint2* src = got.pairs.data() + d.out_base + (cap - len);
             const uint32_t* o1 = pl->order[0].data() + d.node_base[0];
             const uint32_t* o2 = pl->order[1].data() + d.node_base[1];
-            for (uint32_t t = 0; t < len[i]; ++t) {
+            for (uint32_t t = 0; t < len; ++t) {
                 // rank+1 -> local id -> (translate, src/alignment.cpp:26-39) caller id
                 uint64_t a = CL_GAP, b = CL_GAP;
                 if (src[t].x) { a = o1[src[t].x - 1]; if (pl->has_back[0]) a = pl->back[0][nb1 + a]; }
@@ -558,7 +523,7 @@ int cl_stitch_plan_collect(cl_context* ctx, cl_stitch_plan* pl, cl_stitch_result
                 out->pairs[2 * cur + 1] = b;
                 ++cur;
             }
-            out->score[k] = score[i];
+            out->score[k] = got.score[i];
         } else if (pl->route[k] != CL_ROUTE_PURE_DELETION_1 && pl->route[k] != CL_ROUTE_PURE_DELETION_2) {
             for (const auto& pr : pl->host_aln[k]) {
                 uint64_t a = pr.first, b = pr.second;
@@ -666,7 +631,6 @@ static int run_chunk(cl_context* ctx, const cl_stitch_batch* batch, const cl_sti
     cl_stitch_plan* pl = nullptr;
     int rc = cl_stitch_plan_create(ctx, batch, sp, force, &pl);
     if (rc) return rc;
-    pl->graph_tried = true;   // executed once: capturing and instantiating a hipGraph costs more than the launches it would save
     lap("plan (host + upload)");
     rc = cl_stitch_plan_execute(ctx, pl);
     if (!rc && timing) { (void)hipStreamSynchronize(ctx->stream); lap("execute (device)"); }

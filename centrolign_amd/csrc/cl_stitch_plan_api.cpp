@@ -527,7 +527,7 @@ static uint32_t lane_round_waves(uint64_t n_problems) {
     return n_problems >= 2048 ? 3u : 4u;
 }
 // two chain pairs of 17-32 rows per wave (popoa_linear_duo_kernel): alone on the device 32 x 32 pairs run at 215 instead of 130 G cells/s — but the step of 10 x 1 Mbp
-// gets SLOWER with it, 1.79-1.96 against 1.54-1.65 ms (five runs each, profiles/r05_step_spread.txt): the 17 000 such pairs cost the one-pair-per-wave launch nothing
+// gets SLOWER with it, 1.79-1.96 against 1.54-1.65 ms (five runs each, docs/design/removed_switch_records/r05_step_spread.txt): the 17 000 such pairs cost the one-pair-per-wave launch nothing
 // there (it lasts as long as its longest thin pair, 0.43 ms with or without them) and their workgroups fill idle SIMD slots beside the latency-bound launches; taken out,
 // they are one launch more in the step.  So: in plans that have the device to themselves (fewer than 2 048 subproblems), as the register kernel's rounds of four.
 // ... or in which such pairs are at least half of everything (a batch of them alone).  CL_LINEAR_DUOS=0|1 forces.  (-1: decided once the plan is packed)
@@ -547,11 +547,9 @@ struct PackSwitches {
     bool no_sys = false;               // CL_NO_SYS: no systolic DAG kernel (choose_sys)
     bool no_strip = false;             // CL_NO_STRIP: no strips of rows for large pairs, popoa_strip_kernel (choose_chain, choose_lane, fit_strips)
     bool no_ring = false;              // CL_NO_RING: HBM-plane general kernel only (choose_ring)
-    uint8_t lin_mid = 4, lin_big = 0;  // CL_LINEAR_WAVES_MID, CL_LINEAR_WAVES_BIG (choose_chain)
     bool span = true;                  // CL_LINEAR_SPAN (choose_chain)
     bool lane_wide = false;            // CL_LANE_WIDE (choose_lane)
     uint64_t lane_max_rows = 1024, lane_min_sweep = 512;   // CL_LANE_MAX_ROWS, CL_LANE_MIN_SWEEP (choose_lane)
-    bool no_quads = false;             // CL_NO_LINEAR_QUADS (choose_chain), once per process
     uint64_t strip_rows = 0;           // CL_STRIP_ROWS (fit_strips), once per process
 };
 PackSwitches read_pack_switches(uint64_t n_problems) {
@@ -565,18 +563,11 @@ PackSwitches read_pack_switches(uint64_t n_problems) {
     sw.no_sys = is_one(getenv("CL_NO_SYS"));
     sw.no_strip = is_one(getenv("CL_NO_STRIP"));
     sw.no_ring = is_one(getenv("CL_NO_RING"));
-    auto waves_or = [](const char* e, int dflt) { const int v = e ? atoi(e) : 0; return (uint8_t)(v == 3 || v == 4 || v == 8 || v == 16 ? v : dflt); };
-    sw.lin_mid = waves_or(getenv("CL_LINEAR_WAVES_MID"), 4);
-    sw.lin_big = waves_or(getenv("CL_LINEAR_WAVES_BIG"), 0);
     sw.span = [] { const char* e = getenv("CL_LINEAR_SPAN"); return !e || e[0] != '0'; }();   // (read per plan: the tests of the older routes switch it)
     sw.lane_wide = [] { const char* e = getenv("CL_LANE_WIDE"); return e && *e == '1'; }();
     sw.lane_max_rows = [] { const char* e = getenv("CL_LANE_MAX_ROWS"); const long v = e ? atol(e) : 1024; return (uint64_t)(v < 1 ? 1 : v > 1024 ? 1024 : v); }();
     sw.lane_min_sweep = [] { const char* e = getenv("CL_LANE_MIN_SWEEP"); return e ? (uint64_t)atoll(e) : (uint64_t)512; }();   // (read per plan: tests)
-
-
-    static const bool no_quads = [] { const char* e = getenv("CL_NO_LINEAR_QUADS"); return e && *e == '1'; }();
     static const uint64_t rows_env = [] { const char* e = getenv("CL_STRIP_ROWS"); const long v = e ? atol(e) : 0; return (uint64_t)(v >= 64 && v <= 768 ? v / 64 * 64 : 0); }();
-    sw.no_quads = no_quads;
     sw.strip_rows = rows_env;
     return sw;
 }
@@ -693,10 +684,8 @@ bool pack_side(const GraphView& g, int s, uint64_t k, int rank_order, PackPart& 
 // twenty compute units instead — 6 300 x 6 300: 22.4 -> ≈ 12 ms; such a pair always meets the strip kernel's conditions)
 // round 6: chain pairs of more than 1 024 rows span SEVERAL workgroups (popoa_linear_span_kernel, popoa_linear.hip: groups of four strips on different compute units, one
 // round): 2 048 x 2 048 and 6 300 x 6 300 leave the sixteen-wave workgroup's rounds / the DAG strip kernel.  CL_LINEAR_SPAN=0: the routing of rounds 4-5 (A/B)
-// waves of popoa_linear_kernel's workgroup for chain pairs of 65-256 rows / above (rounds of W strips): CL_LINEAR_WAVES_MID=3|4 [4], CL_LINEAR_WAVES_BIG=3|4|8|16
-// [8 up to 512 rows, 16 above].  Measured (profiles/r05_linear_waves_ab.txt): the timed step of 10 x 1 Mbp 2.29-2.31 ms with sixteen waves for every pair above 256
-// rows, 2.16-2.22 with eight, 2.15-2.24 with four, 2.16-2.19 with three; alone on the device 512^2 x 150 runs the same with 16 / 8 / 4 (105 G cells/s), 2 048^2 x 10
-// 15.9 / 14.3 / 10.4 G cells/s — so eight where eight strips are all there are, sixteen above.  Three waves for 65-256 rows: slower in the step (2.25-2.37)
+// waves of popoa_linear_kernel's workgroup (rounds of W strips): four for chain pairs of 65-256 rows, eight up to 512 rows, sixteen above (what other counts
+// measured: docs/design/stitch_kernels.md, "tried and removed")
 struct ChainChoice {
     bool taken = false;
     ChainShape shape;
@@ -716,12 +705,12 @@ ChainChoice choose_chain(uint32_t n1, uint32_t n2, bool linear, const PackInput&
     c.rows_per_lane = 1;
     const bool no_duos = sw.duos == 0;   // (whether the plan takes the duo kernel at all is decided when every pair is known: decide_duos)
     if (span_linear) c.shape = {LaunchVariant::ChainSpan, 0};   // (the pair's strips over several workgroups)
-    else if (nshort <= 16 && !sw.no_quads) c.shape = {LaunchVariant::Quads, 0};   // (FOUR pairs per wave, 16 lanes each — popoa_linear_quad_kernel; CL_NO_LINEAR_QUADS=1: one pair per wave as in rounds 1-4)
+    else if (nshort <= 16) c.shape = {LaunchVariant::Quads, 0};   // (FOUR pairs per wave, 16 lanes each — popoa_linear_quad_kernel)
     else if (nshort <= 32 && !no_duos) c.shape = {LaunchVariant::Duos, 0};   // (TWO pairs per wave, 32 lanes each — popoa_linear_duo_kernel; see duos_forced)
     else if (nshort <= 64) c.shape = {LaunchVariant::Chain, 1};
     else if (nshort <= 128 && nlong < 300) { c.rows_per_lane = 2; c.shape = {LaunchVariant::Chain, 1}; }
-    else if (nshort <= 256) c.shape = {LaunchVariant::Chain, sw.lin_mid};
-    else c.shape = {LaunchVariant::Chain, (uint8_t)(sw.lin_big ? sw.lin_big : (nshort <= 512 || in.n >= 2048) ? 8 : 16)};   // (up to eight strips: eight waves — with sixteen, half of them only stand at the barriers; above, sixteen only in plans that have the device to themselves: the one such pair of the 10 x 1 Mbp step as a launch of its own costs the step 3 %, 1.61 against 1.56 ms, three runs each)
+    else if (nshort <= 256) c.shape = {LaunchVariant::Chain, 4};
+    else c.shape = {LaunchVariant::Chain, (uint8_t)((nshort <= 512 || in.n >= 2048) ? 8 : 16)};   // (up to eight strips: eight waves — with sixteen, half of them only stand at the barriers; above, sixteen only in plans that have the device to themselves: the one such pair of the 10 x 1 Mbp step as a launch of its own costs the step 3 %, 1.61 against 1.56 ms, three runs each)
     c.pad = (uint16_t)((c.swap ? 1 : 0) | (c.rows_per_lane << 1));
     return c;
 }
@@ -1222,8 +1211,7 @@ struct LaunchLists {
 // what forming the groups reads from the environment (what each means: at the function that uses it)
 struct GroupSwitches {
     uint32_t lds_class[5];   // CL_STITCH_LDS_CLASSES, read per plan
-    uint32_t split_at;       // CL_STITCH_SPLIT; this and the rest once per process
-    bool persistent, lane_long_split, merge_lds, block128, merge_all, narrow;   // CL_STITCH_PERSISTENT, CL_LANE_LONG, CL_STITCH_MERGE_LDS, CL_SYS_BLOCK128, CL_STITCH_MERGE_ALL, CL_STITCH_NARROW
+    bool persistent, block128, narrow;   // CL_STITCH_PERSISTENT, CL_SYS_BLOCK128, CL_STITCH_NARROW, once per process
 };
 GroupSwitches read_group_switches() {
     GroupSwitches gs;
@@ -1233,16 +1221,10 @@ GroupSwitches read_group_switches() {
         unsigned a = 0, b = 0, c = 0, d = 0;
         if (sscanf(e, "%u,%u,%u,%u", &a, &b, &c, &d) == 4 && a < b && b < c && c < d && d * 1024u < (uint32_t)kSysLdsBytes) { gs.lds_class[0] = a * 1024; gs.lds_class[1] = b * 1024; gs.lds_class[2] = c * 1024; gs.lds_class[3] = d * 1024; }
     }
-
-
-    static const uint32_t split_at = [] { const char* e = getenv("CL_STITCH_SPLIT"); const long v = e ? atol(e) : 0; return (uint32_t)(v < 0 ? 0 : v); }();
     static const bool persistent = [] { const char* e = getenv("CL_STITCH_PERSISTENT"); return !e || e[0] != '0'; }();
-    static const bool lane_long_split = [] { const char* e = getenv("CL_LANE_LONG"); return e && e[0] == '1'; }();
-    static const bool merge_lds = [] { const char* e = getenv("CL_STITCH_MERGE_LDS"); return !e || e[0] != '0'; }();
     static const bool block128 = [] { const char* e = getenv("CL_SYS_BLOCK128"); return e && e[0] == '1'; }();
-    static const bool merge_all = [] { const char* e = getenv("CL_STITCH_MERGE_ALL"); return e && e[0] == '1'; }();
     static const bool narrow_on = [] { const char* e = getenv("CL_STITCH_NARROW"); return !e || e[0] != '0'; }();
-    gs.split_at = split_at; gs.persistent = persistent; gs.lane_long_split = lane_long_split; gs.merge_lds = merge_lds; gs.block128 = block128; gs.merge_all = merge_all; gs.narrow = narrow_on;
+    gs.persistent = persistent; gs.block128 = block128; gs.narrow = narrow_on;
     return gs;
 }
 
@@ -1373,27 +1355,17 @@ void merge_persistent_chain(cl_stitch_plan& pl, LaunchLists& L, Capacity residen
     pl.groups.push_back(merged);
 }
 // near-chain pairs in registers: one launch per workgroup shape as well (strips of 64 rows over 1 / 4 / 16 waves), longest sweep first
-// The LONG sweeps (1 024 steps and more: a handful of pairs that bound the pass) get launches of their own whose workgroups ask for more than half a compute
-// unit's LDS: one workgroup per compute unit, so that a long sweep's waves do not share their SIMDs with another pair's (190 registers per lane leave room for two
-// waves per SIMD, and two waves on a SIMD each run at half speed — for a launch that lasts as long as its longest sweep that doubles its duration).
-// CL_LANE_LONG=1 switches the split on.  Measured (10 x 1 Mbp, the timed step): it does not pay — 2.69 ms per step with it, 2.46 without at the default
-// routing threshold: the compute units of the long launches are shared with the OTHER kernels' workgroups anyway, and one launch more queues on the streams
-void form_lane_groups(cl_stitch_plan& pl, const Packed& pk, LaunchLists& L, uint32_t lane_rw, bool lane_long_split) {
-    for (int gi = 0; gi < 6; ++gi) {
+void form_lane_groups(cl_stitch_plan& pl, const Packed& pk, LaunchLists& L, uint32_t lane_rw) {
+    for (int waves : {0, (int)lane_rw, 1}) {   // (one wave per SIMD; no launches of eight waves any more)
         LaunchGroup grp;
-        const int lane_waves[3] = {0, (int)lane_rw, 1};   // (one wave per SIMD; no launches of eight waves any more)
-        const bool long_ones = gi < 3;
-        grp.variant = LaunchVariant::Lane; grp.waves = lane_waves[gi % 3];
+        grp.variant = LaunchVariant::Lane; grp.waves = waves;
         grp.first = (uint32_t)L.plist.size();
         for (uint32_t i = 0; i < pl.desc.size(); ++i) {
             const ClProbDesc& d = pl.desc[i];
             const uint32_t rows = std::min(d.n1, d.n2);
-            const bool is_long = lane_long_split && sweep_of(d) >= 1024;
-            if (d.kind == CL_KIND_LANE && !((d.pad >> 8) & 0x7Fu) && (rows <= 64 ? 1 : (int)lane_rw) == grp.waves && is_long == long_ones) { L.plist.push_back(i); grp.ring_bytes = std::max<uint32_t>(grp.ring_bytes, pk.ring_need[i]); }
+            if (d.kind == CL_KIND_LANE && !((d.pad >> 8) & 0x7Fu) && (rows <= 64 ? 1 : (int)lane_rw) == grp.waves) { L.plist.push_back(i); grp.ring_bytes = std::max<uint32_t>(grp.ring_bytes, pk.ring_need[i]); }
         }
-        if (!finish_group(pl, L, grp, [](const ClProbDesc& d) { return sweep_of(d) + 96ull * (std::min(d.n1, d.n2) / 64); })) continue;
-        if (long_ones) grp.ring_bytes = std::max<uint32_t>(grp.ring_bytes, 81u * 1024u);   // more than half of 160 KB: one workgroup per compute unit
-        pl.groups.push_back(grp);
+        if (finish_group(pl, L, grp, [](const ClProbDesc& d) { return sweep_of(d) + 96ull * (std::min(d.n1, d.n2) / 64); })) pl.groups.push_back(grp);
     }
 }
 // The two families whose pairs take several workgroups each that wait for one another: a pair's workgroups are consecutive workgroups of one launch — whole pairs,
@@ -1461,36 +1433,12 @@ void form_general_groups(cl_stitch_plan& pl, const Packed& pk, LaunchLists& L) {
                 if (finish_group(pl, L, grp, cells_of)) pl.groups.push_back(grp);
             }
 }
-// A launch of thousands of workgroups is bound by throughput, not by its longest sweep, and inside a step that shares the device it lasts twice as long as alone
-// (10 x 1 Mbp: 2 651 pairs of the systolic kernel, 0.70 ms alone, 1.45-1.5 ms in the step — the longest launch of the step, alone on its stream).  Such a
-// launch is dealt into PARTS (every parts-th pair of the list by size, so that the parts are alike) which the streams can take separately.
-// CL_STITCH_SPLIT=<workgroups per part> [0: never]
-// Measured (profiles/r05_step_spread.txt): it LOSES — 1.58-1.59 ms per step undivided, 1.70-1.81 in parts of 1 400, 1.87-1.99 in parts of 900 (more launches
-// on the same eight streams cost more than the better balance brings) — so off by default
-void push_sys_group(cl_stitch_plan& pl, LaunchLists& L, LaunchGroup grp, uint32_t split_at) {
-    if (!finish_group(pl, L, grp, cells_of)) return;
-    const uint32_t parts = split_at && grp.count > split_at + split_at / 2 ? (grp.count + split_at - 1) / split_at : 1;
-    if (parts <= 1) { pl.groups.push_back(grp); return; }
-    std::vector<uint32_t> all(L.plist.begin() + grp.first, L.plist.end());
-    L.plist.resize(grp.first);
-    for (uint32_t part = 0; part < parts; ++part) {
-        LaunchGroup sub = grp;
-        sub.first = (uint32_t)L.plist.size();
-        sub.cells = sub.bytes = 0;
-        for (size_t i = part; i < all.size(); i += parts) {
-            L.plist.push_back(all[i]);
-            add_work(sub, pl.desc[all[i]]);
-        }
-        sub.count = (uint32_t)L.plist.size() - sub.first;
-        pl.groups.push_back(sub);
-    }
-}
 // systolic DAG kernel: (NumPW, workgroup size, LDS class) — a launch's dynamic LDS is that of its hungriest problem, and LDS decides
 // how many workgroups share a CU, so the many small problems must not ride with the few large ones
 // CL_STITCH_LDS_CLASSES=a,b,c,d (KB; four boundaries below the ceiling) for measurements
 // ... unless the smaller ones are so few that all workgroups of the merged launch are resident at once anyway: a launch lasts as long as its longest sweep
 // whatever rides along, and every launch less is a millisecond less on the stream it would have occupied (the streams, not the device, are what a step
-// runs out of: 10 x 1 Mbp, sixteen launches a step on eight streams).  CL_STITCH_MERGE_LDS=0: one launch per class as in rounds 2-3 (A/B)
+// runs out of: 10 x 1 Mbp, sixteen launches a step on eight streams)
 // workgroup sizes of the systolic kernel: 64 / 128 / 256 / 1024 threads (round 6: pairs of 65-128 rows — two thirds of the subproblems that used to take 256 threads in
 // the step of 10 x 1 Mbp — get two waves instead of four: a barrier between two waves, no idle waves at it).  CL_SYS_BLOCK128=1 for measurements
 // (measured and lost: 1.51-1.52 -> 1.61-1.68 ms per step — two more launches on the step's streams; off unless asked for)
@@ -1511,6 +1459,7 @@ void form_sys_groups(cl_stitch_plan& pl, const Packed& pk, LaunchLists& L, const
             }
             LaunchGroup grp;
             auto open = [&]() { grp = LaunchGroup(); grp.variant = LaunchVariant::Sys; grp.npw = npw; grp.block = sys_blocks[bi]; grp.first = (uint32_t)L.plist.size(); };
+            auto close = [&]() { if (finish_group(pl, L, grp, cells_of)) pl.groups.push_back(grp); };
             open();
             for (int lc = 4; lc >= 0; --lc) {
                 if (of_class[lc].empty()) continue;
@@ -1520,15 +1469,14 @@ void form_sys_groups(cl_stitch_plan& pl, const Packed& pk, LaunchLists& L, const
                     // all resident at once.  (Also merging classes that leave the newcomers' workgroups per compute unit unchanged was measured and lost: 2.75 against
                     // 2.55 ms per step — the long sweeps of the two classes then share a launch's tail)
                     const bool fits = have + of_class[lc].size() <= 256 * per_cu;
-                    // (CL_STITCH_MERGE_ALL=1, measurement: one launch per kernel shape whatever the LDS classes)
-                    if (!gs.merge_all && (!gs.merge_lds || !fits)) { push_sys_group(pl, L, grp, gs.split_at); open(); }
+                    if (!fits) { close(); open(); }
                 }
                 for (uint32_t i : of_class[lc]) {
                     L.plist.push_back(i);
                     grp.ring_bytes = std::max<uint32_t>(grp.ring_bytes, pk.ring_need[i]);
                 }
             }
-            push_sys_group(pl, L, grp, gs.split_at);
+            close();
         }
 }
 // strips of rows: every strip of a pair is a workgroup of the same launch (they wait for one another: at most 224 workgroups per launch, whole pairs)
@@ -1775,7 +1723,7 @@ int cl_stitch_plan_create(cl_context* ctx, const cl_stitch_batch* batch, const c
     form_chain_groups(*pl, L);
     form_quad_duo_groups(*pl, L);
     if (gs.persistent) merge_persistent_chain(*pl, L, [&] { return cl_chain_persistent_capacity(ctx->device); });
-    form_lane_groups(*pl, pk, L, in.sw.lane_rw, gs.lane_long_split);
+    form_lane_groups(*pl, pk, L, in.sw.lane_rw);
     form_wide_lane_groups(*pl, pk, L);
     form_span_groups(*pl, pk, L);
     lap("pack + route");   // (the chain and near-chain families' groups have always been inside this lap: it stays where it was, so that the figures stay comparable)

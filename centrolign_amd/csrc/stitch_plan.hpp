@@ -131,18 +131,16 @@ struct cl_stitch_plan {
     ClScoreParams sparams{};
     cl_plan_stats stats{};
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    bool graph_tried = false;
     std::vector<uint32_t> plist_host;   // the launch groups' subproblem lists (cl_stitch_plan_launch_info)
-    bool executed = false, profiled = false, calibrated = false;
-    int recalibrations_left = -1, concurrent_passes = 0;
+    bool executed = false, profiled = false;
+    bool calibrated = false;     // the launches have been dealt by their durations measured alone (cl_stitch_plan_execute: the first re-deal)
+    int redeals_left = 1;        // ... and how often they are still dealt again by their clocks inside a pass (the second re-deal): once per plan
     uint32_t tick_pass = 0;      // number of the last concurrent pass (ClDeviceBatch::tick_pass), 1 .. 65 535
     bool event_pass = false;     // the pass being enqueued brackets every launch with HIP events (cl_stitch_plan_execute_evented)
-    bool stop_pending = false;   // the last pass's end is not marked on the context's stream yet (lazy join)   // second stage of the launch scheduling: see cl_stitch_plan_execute
+    bool stop_pending = false;   // the last pass's end is not marked on the context's stream yet (lazy join)
 };
 
-// releases the plan's device blocks, events and graph, then the plan (cl_stitch_exec_api.cpp)
+// releases the plan's device blocks and events, then the plan (cl_stitch_exec_api.cpp)
 void cl_stitch_plan_free(cl_stitch_plan* pl);
 struct ClStitchPlanDeleter { void operator()(cl_stitch_plan* pl) const { cl_stitch_plan_free(pl); } };
 typedef std::unique_ptr<cl_stitch_plan, ClStitchPlanDeleter> ClStitchPlanPtr;
