@@ -1386,6 +1386,176 @@ def periods_hist_tsv(spectrum, names, lengths, scope="both"):
     return _periods_text("cl_periods_hist_tsv", spectrum, names, lengths, scope)
 
 
+class StrandsParams(C.Structure):
+    """cl_strands_params"""
+    _fields_ = [("k", C.c_int32), ("window", C.c_uint32), ("want_votes", C.c_int32)]
+
+
+class StrandProfileC(C.Structure):
+    """cl_strand_profile"""
+    _fields_ = [("n_seq", C.c_uint64), ("n_windows", C.c_uint64), ("n_bases", C.c_uint64), ("k", C.c_int32), ("window", C.c_uint32),
+                ("win_off", C.POINTER(C.c_uint64)), ("base_off", C.POINTER(C.c_uint64)), ("kmers", C.POINTER(C.c_uint32)), ("forward", C.POINTER(C.c_uint32)),
+                ("reverse", C.POINTER(C.c_uint32)), ("votes", C.POINTER(C.c_uint8)), ("distinct", C.c_uint64), ("sort_ms", C.c_float), ("vote_ms", C.c_float)]
+
+
+class StrandIntervalC(C.Structure):
+    """cl_strand_interval"""
+    _fields_ = [(name, C.c_uint32) for name in ("sequence", "start", "end", "windows", "forward", "reverse", "flags", "reserved")]
+
+
+STRAND_INTERVAL = np.dtype([(name, np.uint32) for name in ("sequence", "start", "end", "windows", "forward", "reverse", "flags", "reserved")])
+STRAND_WHOLE, STRAND_REFINED = 1, 2   # the bits of an interval's flags
+_STRAND_COUNTERS = ("kmers", "forward", "reverse")
+
+
+def _raw_sequences(sequences):
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+    return raw, (C.c_char_p * max(len(raw), 1))(*raw), np.array([len(s) for s in raw], dtype=np.uint64)
+
+
+def _strand_profile(ctx, sequences, k, window, want_votes):
+    lib = load_library()
+    raw, bufs, lens = _raw_sequences(sequences)
+    n = len(raw)
+    lib.cl_strands_params_default.argtypes = [C.POINTER(StrandsParams)]
+    lib.cl_strands_params_default.restype = None
+    p = StrandsParams()
+    lib.cl_strands_params_default(C.byref(p))
+    for name, v in (("k", k), ("window", window), ("want_votes", want_votes)):
+        if v is not None:
+            setattr(p, name, int(v))
+    lib.cl_strand_profile_free.argtypes = [C.POINTER(StrandProfileC)]
+    lib.cl_strand_profile_free.restype = None
+    out = StrandProfileC()
+    if ctx is None:
+        h = None
+        lib.cl_strand_profile_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(StrandsParams), C.POINTER(StrandProfileC)]
+        rc = lib.cl_strand_profile_host(bufs, lens.ctypes.data, n, C.byref(p), C.byref(out))
+    else:
+        h = _ctx_handle(ctx)
+        lib.cl_strand_profile_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(StrandsParams), C.POINTER(StrandProfileC)]
+        rc = lib.cl_strand_profile_compute(h, bufs, lens.ctypes.data, n, C.byref(p), C.byref(out))
+    if rc != 0:
+        _raise_last(lib, rc, h)
+    try:
+        G, B = int(out.n_windows), int(out.n_bases)
+        res = {"n_seq": int(out.n_seq), "n_windows": G, "n_bases": B, "k": int(out.k), "window": int(out.window),
+               "win_off": np.ctypeslib.as_array(out.win_off, shape=(n + 1,)).copy(), "base_off": np.ctypeslib.as_array(out.base_off, shape=(n + 1,)).copy(),
+               "votes": np.frombuffer(C.string_at(out.votes, B), dtype=np.uint8).copy() if out.votes else None,
+               "distinct": int(out.distinct), "sort_ms": float(out.sort_ms), "vote_ms": float(out.vote_ms)}
+        for name in _STRAND_COUNTERS:
+            res[name] = np.frombuffer(C.string_at(getattr(out, name), 4 * G), dtype=np.uint32).copy()
+        return res
+    finally:
+        lib.cl_strand_profile_free(C.byref(out))
+
+
+def strand_profile_host(sequences, k=None, window=None, want_votes=None):
+    """cl_strand_profile_host (host only, the definition): the strand profile of `sequences` (str or bytes) as a dict of n_seq, n_windows, n_bases,
+    k, window, win_off / base_off [n + 1] uint64, kmers / forward / reverse [n_windows] uint32, votes [n_bases] uint8 (0 no k-mer, 1 forward,
+    2 reverse, 3 neutral; None with want_votes=0), distinct and the two device times (0 here).  None: the value of cl_strands_params_default
+    (k 21, window 1000, want_votes 1)"""
+    return _strand_profile(None, sequences, k, window, want_votes)
+
+
+def strand_profile(ctx, sequences, k=None, window=None, want_votes=None):
+    """cl_strand_profile_compute: the same on the device, byte for byte"""
+    if ctx is None:
+        raise ValueError("strand_profile needs a context (strand_profile_host is the host call)")
+    return _strand_profile(ctx, sequences, k, window, want_votes)
+
+
+def _strand_profile_c(profile):
+    """a strand_profile dict as the C structure, with the arrays that keep it alive"""
+    n, G, B = profile["n_seq"], profile["n_windows"], profile["n_bases"]
+    keep = {name: np.ascontiguousarray(profile[name], dtype=np.uint32) for name in _STRAND_COUNTERS}
+    keep["win_off"] = np.ascontiguousarray(profile["win_off"], dtype=np.uint64)
+    keep["base_off"] = np.ascontiguousarray(profile["base_off"], dtype=np.uint64)
+    keep["votes"] = None if profile["votes"] is None else np.ascontiguousarray(profile["votes"], dtype=np.uint8)
+    if any(len(keep[name]) != G for name in _STRAND_COUNTERS) or len(keep["win_off"]) != n + 1 or len(keep["base_off"]) != n + 1 or \
+            int(keep["win_off"][n]) != G or int(keep["base_off"][n]) != B or (keep["votes"] is not None and len(keep["votes"]) != B):
+        raise ValueError("the arrays of the profile do not have the sizes it names")
+    pr = StrandProfileC(n_seq=n, n_windows=G, n_bases=B, k=profile["k"], window=profile["window"], distinct=profile["distinct"])
+    pr.win_off = keep["win_off"].ctypes.data_as(C.POINTER(C.c_uint64))
+    pr.base_off = keep["base_off"].ctypes.data_as(C.POINTER(C.c_uint64))
+    for name in _STRAND_COUNTERS:
+        setattr(pr, name, keep[name].ctypes.data_as(C.POINTER(C.c_uint32)))
+    if keep["votes"] is not None:
+        pr.votes = keep["votes"].ctypes.data_as(C.POINTER(C.c_uint8))
+    return pr, keep
+
+
+def strand_intervals(profile, min_run=1):
+    """cl_strand_intervals (host only): the inverted intervals of a strand_profile dict as an array of STRAND_INTERVAL, in sequence order"""
+    lib = load_library()
+    pr, keep = _strand_profile_c(profile)
+    lib.cl_strand_intervals.argtypes = [C.POINTER(StrandProfileC), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.cl_strand_intervals_free.argtypes = [C.c_void_p]
+    lib.cl_strand_intervals_free.restype = None
+    if not 0 <= int(min_run) < 2 ** 32:
+        raise ValueError("min_run is an unsigned 32-bit number")
+    found, count = C.c_void_p(), C.c_uint64()
+    rc = lib.cl_strand_intervals(C.byref(pr), int(min_run), C.byref(found), C.byref(count))
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return np.frombuffer(C.string_at(found.value, 32 * count.value), dtype=STRAND_INTERVAL).copy()
+    finally:
+        lib.cl_strand_intervals_free(found)
+
+
+def strand_apply(sequences, intervals):
+    """cl_strand_apply (host only) on every sequence: the sequences (bytes) with their intervals of `intervals` reverse-complemented in place"""
+    lib = load_library()
+    raw = _raw_sequences(sequences)[0]
+    iv = np.ascontiguousarray(intervals, dtype=STRAND_INTERVAL)
+    lib.cl_strand_apply.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p]
+    turned = []
+    for i, s in enumerate(raw):
+        out = C.create_string_buffer(max(len(s), 1))
+        rc = lib.cl_strand_apply(s, len(s), i, iv.ctypes.data, len(iv), out)
+        if rc != 0:
+            _raise_last(lib, rc)
+        turned.append(out.raw[:len(s)])
+    return turned
+
+
+def _strand_text(call):
+    text, ln = C.c_void_p(), C.c_uint64()
+    lib = load_library()
+    rc = call(lib, C.byref(text), C.byref(ln))
+    if rc != 0:
+        _raise_last(lib, rc)
+    try:
+        return C.string_at(text.value, ln.value)
+    finally:
+        _libc_free(text)
+
+
+def strand_profile_tsv(profile, names):
+    """cl_strand_profile_tsv (host only): the window rows of a strand_profile dict as bytes"""
+    if len(names) != profile["n_seq"]:
+        raise ValueError("%d names for %d sequences" % (len(names), profile["n_seq"]))
+    pr, keep = _strand_profile_c(profile)
+    arr = (C.c_char_p * max(len(names), 1))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names])
+
+    def call(lib, text, ln):
+        lib.cl_strand_profile_tsv.argtypes = [C.POINTER(StrandProfileC), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        return lib.cl_strand_profile_tsv(C.byref(pr), arr, text, ln)
+    return _strand_text(call)
+
+
+def strand_intervals_tsv(intervals, names):
+    """cl_strand_intervals_tsv (host only): the rows of an array of STRAND_INTERVAL as bytes; names[i] is the name of sequence i"""
+    iv = np.ascontiguousarray(intervals, dtype=STRAND_INTERVAL)
+    arr = (C.c_char_p * max(len(names), 1))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names])
+
+    def call(lib, text, ln):
+        lib.cl_strand_intervals_tsv.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        return lib.cl_strand_intervals_tsv(iv.ctypes.data, len(iv), arr, len(names), text, ln)
+    return _strand_text(call)
+
+
 class MonomersParams(C.Structure):
     """cl_monomers_params"""
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("insertion", C.c_int32), ("deletion", C.c_int32), ("chunk", C.c_uint32), ("overlap", C.c_uint32),
@@ -2314,6 +2484,8 @@ EXPORTED_SYMBOLS = [
     "cl_monomer_decomposition_free",
     "cl_monomer_pileup_host", "cl_monomer_pileup_compute", "cl_monomer_pileup_free", "cl_monomer_consensus", "cl_monomer_templates_refine_host",
     "cl_monomer_templates_refine_compute", "cl_monomer_templates_free", "cl_monomer_seed_templates", "cl_monomer_pileup_tsv", "cl_monomer_templates_fasta",
+    "cl_strands_params_default", "cl_strand_profile_host", "cl_strand_profile_compute", "cl_strand_profile_free", "cl_strand_intervals",
+    "cl_strand_intervals_free", "cl_strand_apply", "cl_strand_profile_tsv", "cl_strand_intervals_tsv",
 ]
 
 

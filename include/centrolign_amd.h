@@ -1317,7 +1317,77 @@ int  cl_monomer_pileup_tsv(const cl_monomer_pileup* pileup, const char* const* t
 int  cl_monomer_templates_fasta(const char* const* names, const char* const* templates, const uint64_t* template_lengths, uint64_t n_templates,
                                 char** text_out, uint64_t* len_out /* may be NULL */);
 
-/* --- the control plane: the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
+/* --- strand profiles: inverted intervals and flipped sequences (the tool centrolign-orient; the reference has none) ---------------------------
+ * The reference aligns globally and "does not identify inversions" (its README, Limitations).  This is the layer in front of it: per window of
+ * every input sequence, how many k-mers stand on the strand of the majority of the input and how many on the other; from that the inverted
+ * intervals; and the input with those intervals turned back.  Every number is an integer and nothing depends on scheduling.
+ * k-mers and windows as for the period spectra: k characters of ACGTacgt, case-folded, inside one sequence; a k-mer belongs to the window
+ *   floor(p / window) of its first base p.  rc(x) is the reverse complement of x; count(x) the number of positions of the whole call whose
+ *   k-mer is x.
+ * Vote of an occurrence of x, with a = count(x), b = count(rc(x)): neutral if a + b < 2 (seen once, no reverse complement anywhere); else
+ *   forward if a > b, reverse if b > a, neutral if a = b.  A palindrome (x = rc(x), even k) has a = b: neutral.  The strand is relative to the
+ *   majority of the input's own k-mer occurrences: of two sequences of which one is flipped, which one is called is deterministic but arbitrary.
+ * cl_strand_profile: win_off[n_seq + 1] and base_off[n_seq + 1] are the offsets of the sequences' windows and bases; per window kmers (positions
+ *   with a k-mer), forward, reverse (neutral is the rest); with want_votes one byte per base in sequence order, 0 no k-mer, 1 forward, 2 reverse,
+ *   3 neutral, else votes is NULL; distinct is the number of distinct values of min(x, rc(x)).  sort_ms / vote_ms: device time by events of
+ *   the keys, their compaction and sort, and of the runs, votes and window sums; 0 from the host call.
+ * Window call: a window is decided if forward != reverse, and then reverse iff reverse > forward.  An undecided window takes the call of the
+ *   nearest decided window to its left in its sequence, failing that of the nearest to its right; a sequence without a decided window is forward.
+ * Intervals (cl_strand_intervals; host only).  Per sequence, in order, every maximal run [wa, wb) of reverse windows with wb - wa >= min_run
+ *   gives one interval [start, end).  v(p) = +1, -1, 0 for a forward, reverse or other vote at p; prev = the end of the sequence's previous
+ *   interval, or 0; W = window; nw = the sequence's windows.  wa = 0: start = 0.  Else lo = max(prev, (wa - 1) W), hi = min(len, (wa + 1) W) and
+ *   start = the largest c in [lo, hi] that maximises sum(v(p), lo <= p < c) - sum(v(p), c <= p < hi).  wb = nw: end = len.  Else
+ *   lo = max(start, (wb - 1) W), hi = min(len, (wb + 1) W) and end = the largest c in [lo, hi] that maximises -sum(v(p), lo <= p < c) +
+ *   sum(v(p), c <= p < hi).  (The k - 1 k-mers across a clean breakpoint are new to the input, hence neutral, and the breakpoint is the right
+ *   end of the tie.)  forward / reverse of an interval are the votes of the positions in [start, end).  A profile without votes gives the window
+ *   boundaries clipped to the sequence and the run's window sums.  flags: bit 0 the interval is the whole sequence, bit 1 one of its boundaries
+ *   was placed by the votes.
+ * Apply (cl_strand_apply; host only).  out = sequence with every interval whose `sequence` is sequence_index reverse-complemented in place:
+ *   ACGTacgt go to TGCAtgca, any other character is its own complement; applying the same intervals twice returns the input.  out holds length
+ *   bytes and may be `sequence` itself.  Intervals of that sequence that do not fit it, overlap or are out of order are refused before
+ *   anything is written.
+ * Limits.  k in 1..31; window in 1..2^20; min_run >= 1; fewer than 2^28 sequences; the lengths add up to less than 2^30 (checked before a base
+ *   is read); n = 0 and empty sequences are fine.  Anything else is CL_ERR_INVALID_ARGUMENT with a cl_last_error that names the argument.
+ * cl_strand_profile_host: the definition, written plainly on the host; no context, no GPU.  cl_strand_profile_compute: the device path
+ *   (strands_kernels.hip) with the same bytes in every field but the two times.
+ * cl_strand_profile_tsv: host only.  A header line, then sample start end kmers forward reverse neutral call per window, tab-separated; call is
+ *   + or - after the inheritance rule.  cl_strand_intervals_tsv: a header line, then sample start end length windows forward reverse whole
+ *   (whole: 1 or 0); names[] covers every sequence index among the intervals.  Coordinates are 0-based, half-open.  Every line ends with a line
+ *   end; text returned through char** is malloc'ed.
+ * The arrays of a cl_strand_profile and the intervals are malloc'ed: release them with the _free of each. */
+typedef struct cl_strands_params {
+    int32_t  k;             /* 21 */
+    uint32_t window;        /* 1000 */
+    int32_t  want_votes;    /* 1 */
+} cl_strands_params;
+typedef struct cl_strand_profile {
+    uint64_t  n_seq, n_windows, n_bases;
+    int32_t   k;
+    uint32_t  window;
+    uint64_t* win_off;                       /* [n_seq + 1] */
+    uint64_t* base_off;                      /* [n_seq + 1] */
+    uint32_t *kmers, *forward, *reverse;     /* [n_windows] each */
+    uint8_t*  votes;                         /* [n_bases], NULL with want_votes = 0 */
+    uint64_t  distinct;
+    float     sort_ms, vote_ms;              /* device time by events */
+} cl_strand_profile;
+typedef struct cl_strand_interval {   /* 32 bytes */
+    uint32_t sequence, start, end, windows, forward, reverse, flags, reserved /* 0 */;
+} cl_strand_interval;
+void cl_strands_params_default(cl_strands_params* params);
+int  cl_strand_profile_host(const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_strands_params* params, cl_strand_profile* out);
+int  cl_strand_profile_compute(cl_context* ctx, const char* const* sequences, const uint64_t* lengths, uint64_t n, const cl_strands_params* params,
+                               cl_strand_profile* out);
+void cl_strand_profile_free(cl_strand_profile* out);
+int  cl_strand_intervals(const cl_strand_profile* profile, uint32_t min_run, cl_strand_interval** intervals_out, uint64_t* n_out);
+void cl_strand_intervals_free(cl_strand_interval* intervals);
+int  cl_strand_apply(const char* sequence, uint64_t length, uint64_t sequence_index, const cl_strand_interval* intervals, uint64_t n_intervals,
+                     char* out /* the caller's, length bytes */);
+int  cl_strand_profile_tsv(const cl_strand_profile* profile, const char* const* names, char** text_out, uint64_t* len_out /* may be NULL */);
+int  cl_strand_intervals_tsv(const cl_strand_interval* intervals, uint64_t n_intervals, const char* const* names, uint64_t n_names, char** text_out,
+                             uint64_t* len_out /* may be NULL */);
+
+/* --- the control plane:the CLI's parameters and config files (src/parameters.cpp; cl_config_api.cpp) ---------------------------------
  * A cl_config holds every parameter the reference registers (all 60, in its order and groups), starting from the values its CLI starts
  * from.  Enums are integers.  Parameters are named as in the reference; a value is given and read back as config text (the same parsers
  * a config file goes through: integers whole, booleans true/false/T/F/1/0 in the reference's spellings, arrays as three comma-separated
